@@ -1,12 +1,19 @@
 """Benchmark of the ALPRO hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W [--workload pretrain_step|visual_fwd|pretrain_fwd] [--batch B] [--dtype fp16|bf16|fp32]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times K steps and prints the headline line (metric, value, unit, higher_is_better, dtype, ms_per_step and the
+configuration).  --full adds everything else this file measures, each in passes of its own after the timed steps: the per-kernel-family pass
+(kernel_ms_per_step, roofline), the divST sub-block measurement, the in-run parity against tests/golden and the CPU baseline.
+--dump-outputs DIR writes what the last timed step returned (and, for pretrain_step, a fixed sample of the updated parameters) as
+DIR/<name>.npy in float32 / float64; outputs above 2^19 elements are written as a fixed, seeded sample of 2^19 of them.
 
 Default mode: fp16 operands (fp32 accumulation / residual stream / statistics, dynamic loss scaling for the backward) + the CLS rows of both
 encoders re-evaluated in fp32 (alpro_amd.config.cls_precise, round 4) -- the fastest mode that meets the north star's "VTC logits within
-1e-3 of the reference" on EVERY reference fixture (plain fp16: 1.06e-3 on the worst one; bf16: 9e-3).  The `parity` object of the JSON line
-is MEASURED in this process against all four reference-generated VTC fixtures under tests/golden/ (measure_parity below): `meets_bar` is
-decided by the WORST of them.
+1e-3 of the reference" on EVERY reference fixture (plain fp16: 1.06e-3 on the worst one; bf16: 9e-3).  With --full the `parity` object of the
+JSON line is MEASURED in this process against all four reference-generated VTC fixtures under tests/golden/ (measure_parity below): `meets_bar`
+is decided by the WORST of them.
 
 Default workload: pretrain_step -- the configuration BASELINE.json's metric ("video-text pairs/sec at 1/2/4/8 MI355X") is
 quoted on (configs[2] on one GPU, configs[3] under DP); visual_fwd is configs[1] (encoder-only isolation run).
@@ -467,6 +474,111 @@ def measure_parity(dev, dtype, full_size_backward=False):
     return out
 
 
+DUMP_MAX_ELEMS = 1 << 19        # per array (4 MB at most): larger outputs are written as a fixed, seeded sample of this many elements
+DUMP_PARAM_SAMPLE = 1024        # per trained parameter tensor, for params_sample.npy
+
+
+def _dump_array(t, seed):
+    """(float32 / float64 numpy array of `t`, or of a fixed sample of it drawn with `seed`), on the host."""
+    t = t.detach().reshape(-1)
+    if t.numel() > DUMP_MAX_ELEMS:
+        g = torch.Generator(device="cpu").manual_seed(seed)
+        idx = torch.randint(0, t.numel(), (DUMP_MAX_ELEMS,), generator=g).sort().values
+        t = t[idx.to(t.device)]
+    dt = torch.float64 if t.dtype in (torch.float64, torch.int64, torch.int32) else torch.float32
+    return t.to(dt).cpu().numpy()
+
+
+def dump_outputs(path, outputs, params=None):
+    """Write what the last timed step returned as path/<name>.npy (see DUMP_MAX_ELEMS); `params`: the trained
+    parameters after that step, written as one array of a fixed sample of DUMP_PARAM_SAMPLE elements per tensor, whole tensors when they
+    are not larger (params_sample.npy)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    if torch.is_tensor(outputs):
+        outputs = {"output": outputs}
+    for i, (name, t) in enumerate(sorted(outputs.items())):
+        if torch.is_tensor(t):
+            np.save(os.path.join(path, name + ".npy"), _dump_array(t, seed=i))
+    if params:
+        g = torch.Generator(device="cpu").manual_seed(0)
+        rows = []
+        for p in params:
+            flat = p.detach().reshape(-1)
+            if flat.numel() > DUMP_PARAM_SAMPLE:
+                flat = flat[torch.randint(0, flat.numel(), (DUMP_PARAM_SAMPLE,), generator=g).to(flat.device)]
+            rows.append(flat.float())
+        np.save(os.path.join(path, "params_sample.npy"), torch.cat(rows).cpu().numpy())
+
+
+def kernel_figures(kt, ks, dtype, train, B, T, step_ms):
+    """The roofline object and kernel_ms_per_step of the bench line (--full), from one step under KernelTimer: the MFMA-bound GEMM family
+    against the dense peak, HBM bytes per GEMM launch from the latest committed PMC passes, the dominant GEMM instantiation, the top shapes."""
+    from alpro_amd import hip
+    gemm = dict(ks["gemm"])
+    for fam in ("gemm_tn_acc", "gemm_qkv_tattn"):  # the wgrad GEMMs and the fused qkv + temporal-attention tiles belong to the same MFMA-bound family
+        if fam in ks:
+            for k_ in ("launches", "flops", "ms"):
+                gemm[k_] += ks[fam][k_]
+    ach = gemm["flops"] / (gemm["ms"] * 1e-3) / 1e12
+    traffic, traffic_src, pm = None, None, {}
+    import glob
+    import re
+    profs = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pretrain_step_B64_pmc_traffic.json")),
+                   key=lambda f: (int(re.match(r"r(\d+)", os.path.basename(f)).group(1)), os.path.basename(f)))
+    prof = profs[-1] if profs else ""  # the latest round's PMC passes
+    if train and B == 64 and T == 8 and dtype in ("bf16", "fp16") and prof:
+        # HBM bytes per GEMM launch from the committed rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this same command
+        # (tools/pmc_summary.py; FETCH_SIZE doubled per MI355X_MICROARCH.md): launch-weighted mean over the GEMM kernels
+        pm = {k_.replace("alpro::", ""): v_ for k_, v_ in json.load(open(prof)).items()}
+        gk = {k: v for k, v in pm.items() if k.startswith("gemm_")}
+        n = sum(v["launches"] for v in gk.values())
+        traffic = round(sum(v["launches"] * (v["read_bytes_corrected_per_launch"] + v["write_bytes_per_launch"]) for v in gk.values()) / n)
+        traffic_src = "profiles/" + os.path.basename(prof)
+    peak = MFMA_PEAK_TFLOPS[dtype]
+    # the single dominant kernel INSTANTIATION (VERDICT r3 item 7): NT GEMM launches grouped by the template arguments the library picks --
+    # persistent 256x256 kernel from 160 tiles up, activation, row map (gemm.hip launch_gemm_inst) -- with their own FLOPs, time and PMC bytes
+    import re as _re
+    inst = {}
+    for (name, key), (c, f, ms_) in kt.shapes.items():
+        if name != "gemm":
+            continue
+        mm = _re.match(r"M=(\d+) N=(\d+) K=(\d+) act=(\S+) res=(\d) out=(\S+) map=(\S+)", key)
+        M_, N_, K_ = int(mm.group(1)), int(mm.group(2)), int(mm.group(3))
+        big = ((N_ + 255) // 256) * ((M_ + 255) // 256) >= 160 and K_ >= 128
+        tname = {"fp16": "f16_t", "bf16": "bf16_t", "fp32": "float"}[dtype]
+        # round 4: identity-map 16-bit shapes with whole 256-column tiles and an even number >= 4 of K-tiles run on the 8-phase kernel --
+        # 16-bit outputs with any epilogue, fp32 outputs with the plain (bias / row scale / residual) one; a ragged last tile row included
+        q_ok = (dtype != "fp32" and mm.group(7) == "0" and N_ % 256 == 0 and K_ % 128 == 0 and K_ >= 256 and (N_ // 256) * (M_ // 256) >= 160
+                and (mm.group(6) != "float32" or mm.group(4) == "0") and hip.get_option("gemm_kind") == 1)
+        if q_ok:
+            kn = "gemm_nt256q_kernel<%s, %s, 0>" % (tname, mm.group(4))
+        else:
+            kn = "%s<%s, %s, %s%s>" % ("gemm_nt256p_kernel" if big else "gemm_nt_kernel", tname, mm.group(4), mm.group(7), ", 1" if big else "")
+        d_ = inst.setdefault(kn, [0, 0.0, 0.0])
+        d_[0] += c
+        d_[1] += f
+        d_[2] += ms_
+    dom = max(inst, key=lambda k_: inst[k_][2]) if inst else None
+    dominant = None
+    if dom:
+        c, f, ms_ = inst[dom]
+        dominant = {"kernel": dom, "launches": c, "gflop_per_launch": round(f / c / 1e9, 2), "avg_launch_ms": round(ms_ / c, 4),
+                    "achieved": round(f / ms_ / 1e9, 1), "peak": peak, "unit": "TFLOP/s", "frac": round(f / ms_ / 1e9 / peak, 4),
+                    "share_of_step": round(ms_ / step_ms, 3), "traffic": None}
+        if traffic_src and dom in pm:
+            dominant["traffic"] = pm[dom]["read_bytes_corrected_per_launch"] + pm[dom]["write_bytes_per_launch"]
+    shapes_tab = [{"op": n_, "shape": k_, "n": c, "ms": round(ms_, 3), "tflops": round(f / ms_ / 1e9, 1)}
+                  for (n_, k_), (c, f, ms_) in sorted(kt.shapes.items(), key=lambda kv: -kv[1][2]) if f > 0][:24]
+    roofline = {"bound": "mfma", "kernel": "gemm_nt*/gemm_tn kernels<%s> (all %d GEMM launches of one step)" % (dtype, gemm["launches"]),
+                "achieved": round(ach, 1), "peak": peak, "unit": "TFLOP/s", "frac": round(ach / peak, 4),
+                "avg_launch_ms": round(gemm["ms"] / gemm["launches"], 4),
+                "gflop_per_launch": round(gemm["flops"] / gemm["launches"] / 1e9, 2), "traffic": traffic,
+                "traffic_unit": "HBM bytes per GEMM launch (PMC)", "traffic_source": traffic_src,
+                "dominant_instance": dominant, "gemm_shapes": shapes_tab}
+    return roofline, {k: round(v["ms"], 3) for k, v in ks.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -482,7 +594,14 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-divst", action="store_true", help="skip the divST sub-block measurement pass (clean per-step rocprof traces)")
     ap.add_argument("--no-parity", action="store_true", help="skip the in-run parity measurement against tests/golden (a few seconds)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the per-kernel pass (kernel_ms_per_step, roofline), the divST sub-block measurement, the "
+                         "in-run parity and the CPU baseline (each can still be left out with the --no-* switches above)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / float64, fixed samples of large outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: become the launcher -- one rank per GPU under torch.distributed.run on this node (RCCL over xGMI),
@@ -553,7 +672,7 @@ def main():
             opt.backward(loss)  # loss.backward(); fp16 operands: the loss carries the dynamic loss scale (apex amp.scale_loss, :596-599)
             opt.step()        # gradient all-reduce (RCCL) + [1 / loss scale, overflow check] + global-norm clip + AdamW
             opt.zero_grad()
-            return loss
+            return dict(out, loss=loss)
         flops_per_unit = 1847e9 * (T / 8.0)  # 877 G forward + 970 G backward per pair
         unit = "pairs/s"
         wl = ("AlproForPretrain training step VTC+VTM+MLM+MPM fwd+bwd+allreduce+clip+AdamW (BASELINE configs[2]/[3]), "
@@ -570,10 +689,14 @@ def main():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            step()
+            last = None       # (a step's outputs are not held across the next one)
+            last = step()
         torch.cuda.synchronize()
         dist.barrier()
         elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:   # before any untimed pass below: what the last timed step left
+        dump_outputs(args.dump_outputs, last, [p for p in model.parameters() if p.requires_grad] if train else None)
+    last = None
     xstats = None
     if train:
         opt.record_exchange = False
@@ -583,86 +706,33 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # per-kernel-family device time: one extra, untimed step under HIP events.  EVERY rank runs it (the training step holds
+    # --full: per-kernel-family device time: one extra, untimed step under HIP events.  EVERY rank runs it (the training step holds
     # collectives: a rank-0-only pass would wait forever for its peers); only rank 0 reports.
     # Launches are timed one at a time on the launch stream: the two-stream forward (alpro_amd.config.split_streams) is off for this pass, so that a
     # kernel's time is its own and not its share of the chip beside the other half's launches.
     from alpro_amd import config as _rt
-    _prev_split, _prev_wgs, _prev_txt = _rt._split_streams[0], _rt.wgrad_stream_enabled(), _rt.text_stream_enabled()
-    _rt.set_split_streams("0")
-    _rt.set_wgrad_stream(False)   # ... and the weight gradients / the text pass stay on the launch stream for the same reason
-    _rt.set_text_stream(False)
-    _prev_ps = _rt.prompter_stream_enabled()
-    _rt.set_prompter_stream(False)
-    try:
-        with (torch.enable_grad() if train else torch.no_grad()), KernelTimer(hip) as kt:
-            step()
-        ks = kt.summary()
-    finally:
-        _rt.set_split_streams(_prev_split)
-        _rt.set_wgrad_stream(_prev_wgs)
-        _rt.set_text_stream(_prev_txt)
-        _rt.set_prompter_stream(_prev_ps)
+    ks = kt = None
+    if args.full:
+        _prev_split, _prev_wgs, _prev_txt = _rt._split_streams[0], _rt.wgrad_stream_enabled(), _rt.text_stream_enabled()
+        _rt.set_split_streams("0")
+        _rt.set_wgrad_stream(False)   # ... and the weight gradients / the text pass stay on the launch stream for the same reason
+        _rt.set_text_stream(False)
+        _prev_ps = _rt.prompter_stream_enabled()
+        _rt.set_prompter_stream(False)
+        try:
+            with (torch.enable_grad() if train else torch.no_grad()), KernelTimer(hip) as kt:
+                step()
+            ks = kt.summary()
+        finally:
+            _rt.set_split_streams(_prev_split)
+            _rt.set_wgrad_stream(_prev_wgs)
+            _rt.set_text_stream(_prev_txt)
+            _rt.set_prompter_stream(_prev_ps)
     dist.barrier()
     result = None
     if rank == 0:
         ms = elapsed / args.steps * 1e3
         value = world * B * args.steps / elapsed
-        gemm = dict(ks["gemm"])
-        for fam in ("gemm_tn_acc", "gemm_qkv_tattn"):  # the wgrad GEMMs and the fused qkv + temporal-attention tiles belong to the same MFMA-bound family
-            if fam in ks:
-                for k_ in ("launches", "flops", "ms"):
-                    gemm[k_] += ks[fam][k_]
-        ach = gemm["flops"] / (gemm["ms"] * 1e-3) / 1e12
-        traffic, traffic_src, pm = None, None, {}
-        import glob
-        import re
-        profs = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pretrain_step_B64_pmc_traffic.json")),
-                       key=lambda f: (int(re.match(r"r(\d+)", os.path.basename(f)).group(1)), os.path.basename(f)))
-        prof = profs[-1] if profs else ""  # the latest round's PMC passes
-        if train and B == 64 and T == 8 and args.dtype in ("bf16", "fp16") and prof:
-            # HBM bytes per GEMM launch from the committed rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this same command
-            # (tools/pmc_summary.py; FETCH_SIZE doubled per MI355X_MICROARCH.md): launch-weighted mean over the GEMM kernels
-            pm = {k_.replace("alpro::", ""): v_ for k_, v_ in json.load(open(prof)).items()}
-            gk = {k: v for k, v in pm.items() if k.startswith("gemm_")}
-            n = sum(v["launches"] for v in gk.values())
-            traffic = round(sum(v["launches"] * (v["read_bytes_corrected_per_launch"] + v["write_bytes_per_launch"]) for v in gk.values()) / n)
-            traffic_src = "profiles/" + os.path.basename(prof)
-        peak = MFMA_PEAK_TFLOPS[args.dtype]
-        # the single dominant kernel INSTANTIATION: NT GEMM launches grouped by the template arguments the library picks --
-        # persistent 256x256 kernel from 160 tiles up, activation, row map (gemm.hip launch_gemm_inst) -- with their own FLOPs, time and PMC bytes
-        import re as _re
-        inst = {}
-        for (name, key), (c, f, ms_) in kt.shapes.items():
-            if name != "gemm":
-                continue
-            mm = _re.match(r"M=(\d+) N=(\d+) K=(\d+) act=(\S+) res=(\d) out=(\S+) map=(\S+)", key)
-            M_, N_, K_ = int(mm.group(1)), int(mm.group(2)), int(mm.group(3))
-            big = ((N_ + 255) // 256) * ((M_ + 255) // 256) >= 160 and K_ >= 128
-            tname = {"fp16": "f16_t", "bf16": "bf16_t", "fp32": "float"}[args.dtype]
-            # round 4: identity-map 16-bit shapes with whole 256-column tiles and an even number >= 4 of K-tiles run on the 8-phase kernel --
-            # 16-bit outputs with any epilogue, fp32 outputs with the plain (bias / row scale / residual) one; a ragged last tile row included
-            q_ok = (args.dtype != "fp32" and mm.group(7) == "0" and N_ % 256 == 0 and K_ % 128 == 0 and K_ >= 256 and (N_ // 256) * (M_ // 256) >= 160
-                    and (mm.group(6) != "float32" or mm.group(4) == "0") and hip.get_option("gemm_kind") == 1)
-            if q_ok:
-                kn = "gemm_nt256q_kernel<%s, %s, 0>" % (tname, mm.group(4))
-            else:
-                kn = "%s<%s, %s, %s%s>" % ("gemm_nt256p_kernel" if big else "gemm_nt_kernel", tname, mm.group(4), mm.group(7), ", 1" if big else "")
-            d_ = inst.setdefault(kn, [0, 0.0, 0.0])
-            d_[0] += c
-            d_[1] += f
-            d_[2] += ms_
-        dom = max(inst, key=lambda k_: inst[k_][2]) if inst else None
-        dominant = None
-        if dom:
-            c, f, ms_ = inst[dom]
-            dominant = {"kernel": dom, "launches": c, "gflop_per_launch": round(f / c / 1e9, 2), "avg_launch_ms": round(ms_ / c, 4),
-                        "achieved": round(f / ms_ / 1e9, 1), "peak": peak, "unit": "TFLOP/s", "frac": round(f / ms_ / 1e9 / peak, 4),
-                        "share_of_step": round(ms_ / (elapsed / args.steps * 1e3), 3), "traffic": None}
-            if traffic_src and dom in pm:
-                dominant["traffic"] = pm[dom]["read_bytes_corrected_per_launch"] + pm[dom]["write_bytes_per_launch"]
-        shapes_tab = [{"op": n_, "shape": k_, "n": c, "ms": round(ms_, 3), "tflops": round(f / ms_ / 1e9, 1)}
-                      for (n_, k_), (c, f, ms_) in sorted(kt.shapes.items(), key=lambda kv: -kv[1][2]) if f > 0][:24]
         result = {
             "metric": "video-text pairs/sec (8f x 224^2, 40-tok)", "value": round(value, 3), "unit": unit, "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 3), "higher_is_better": True, "scaling": "weak",
@@ -688,29 +758,24 @@ def main():
             # the CU count the persistent grids were sized for meanwhile.  Read a SCALE record against these first.
             "exchange": xstats,
             "model_tflops_per_gpu": round(value / world * flops_per_unit / 1e12, 2),
-            "roofline": {"bound": "mfma", "kernel": "gemm_nt*/gemm_tn kernels<%s> (all %d GEMM launches of one step)" % (args.dtype, gemm["launches"]),
-                         "achieved": round(ach, 1), "peak": peak, "unit": "TFLOP/s", "frac": round(ach / peak, 4),
-                         "avg_launch_ms": round(gemm["ms"] / gemm["launches"], 4),
-                         "gflop_per_launch": round(gemm["flops"] / gemm["launches"] / 1e9, 2), "traffic": traffic,
-                         "traffic_unit": "HBM bytes per GEMM launch (PMC)", "traffic_source": traffic_src,
-                         "dominant_instance": dominant, "gemm_shapes": shapes_tab},
-            "kernel_ms_per_step": {k: round(v["ms"], 3) for k, v in ks.items()},
         }
-        if world == 1 and args.dtype in ("bf16", "fp16") and T == 8 and not args.no_divst:  # the north-star kernel target, measured in the same process (~1 s)
+        if args.full:
+            result["roofline"], result["kernel_ms_per_step"] = kernel_figures(kt, ks, args.dtype, train, B, T, ms)
+        if args.full and world == 1 and args.dtype in ("bf16", "fp16") and T == 8 and not args.no_divst:  # the north-star kernel target, measured in the same process (~1 s)
             result["roofline"]["divst_subblock"] = measure_divst(dev, T, model if args.workload == "visual_fwd" else None)
         if train and opt.scaler is not None:
             st = opt.scaler.state.tolist()
             result["loss_scale"] = {"scale": st[0], "applied_steps": int(st[2]), "skipped_steps": int(st[3]), "policy": "dynamic (apex.amp defaults: 2^16, x0.5 on overflow, x2 per 2000 clean steps), device-resident"}
-        if not args.no_parity and world == 1:  # (rank 0 alone would keep its peers waiting at N > 1)
+        if args.full and not args.no_parity and world == 1:  # (rank 0 alone would keep its peers waiting at N > 1)
             model = batch = None
             if train:
                 opt = None
             torch.cuda.empty_cache()
             result["parity"] = measure_parity(dev, args.dtype, full_size_backward=train and B == 64 and T == 8)
-        else:   # (--no-parity, or N > 1 where rank 0 alone cannot run it): say where the measured numbers of this mode live
+        else:   # (a plain run, --no-parity, or N > 1 where rank 0 alone cannot run it): say where the measured numbers of this mode live
             result["parity"] = {"mode": mode_name(args.dtype), "measured_in_this_run": False,
-                                "see": "profiles/r4_parity_pareto.txt (worst-of-four-fixture VTC-logit error and the B=64 proxy per mode), profiles/r5_parity_backward_B64.txt (B=64 backward against the exact fp32 HIP mode); rerun with N=1 and without --no-parity to measure in-process"}
-        if not args.no_cpu_baseline and world == 1:  # reported at N=1 only (rank 0 would keep its peers waiting at N>1)
+                                "see": "profiles/r4_parity_pareto.txt (worst-of-four-fixture VTC-logit error and the B=64 proxy per mode), profiles/r5_parity_backward_B64.txt (B=64 backward against the exact fp32 HIP mode); rerun with --full at N=1 and without --no-parity to measure in-process"}
+        if args.full and not args.no_cpu_baseline and world == 1:  # reported at N=1 only (rank 0 would keep its peers waiting at N>1)
             result["cpu_baseline"] = cpu_baseline_train(T) if train else cpu_baseline(T)
         print(json.dumps(result), flush=True)
     dist.barrier()

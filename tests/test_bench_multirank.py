@@ -1,7 +1,7 @@
 """GPU: bench.py's multi-process path end to end -- two ranks sharing the one GPU of the test box over gloo
 (ALPRO_DIST_BACKEND=gloo; RCCL refuses two ranks on one device).  Exercises what the N>1 driver run exercises: rendezvous,
 parameter broadcast, the differentiable feature all-gather inside forward, the flat gradient all-reduce, the untimed
-per-kernel pass on EVERY rank (a rank-0-only extra step would hang in its collectives) and a clean exit."""
+per-kernel pass of --full on EVERY rank (a rank-0-only extra step would hang in its collectives) and a clean exit."""
 import json
 import os
 import socket
@@ -25,7 +25,7 @@ def test_bench_two_ranks_gloo_shared_gpu(how):
     env = dict(os.environ, ALPRO_DIST_BACKEND="gloo")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    tail = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--batch", "2", "--frames", "2", "--steps", "1", "--warmup", "1"]
+    tail = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--batch", "2", "--frames", "2", "--steps", "1", "--warmup", "1", "--full"]
     if how == "torchrun":
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port)] + tail
     else:
@@ -37,6 +37,7 @@ def test_bench_two_ranks_gloo_shared_gpu(how):
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["value"] > 0 and d["config"]["per_gpu_batch"] == 2
     assert "cpu_baseline" not in d                          # reported at N=1 only
+    assert d["kernel_ms_per_step"]["gemm"] > 0 and d["roofline"]["frac"] > 0   # the --full per-kernel pass ran (on every rank)
     # the N > 1 line diagnoses its own gradient exchange -- one logged exchange per timed step on rank 0, the part that
     # went on the wire from inside backward (the overlapped exchange is the default), what was left for synchronize(), the exposed time
     x = d["exchange"]

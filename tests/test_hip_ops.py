@@ -567,7 +567,8 @@ def _cu_thief():
     """tools/cu_thief.hip (n resident workgroups with 64 KiB of LDS each: the footprint of a collective's channel kernels), built on the box."""
     import ctypes
     import subprocess
-    so = "/tmp/libcu_thief_test.so"
+    import tempfile
+    so = os.path.join(tempfile.mkdtemp(prefix="alpro_test_"), "libcu_thief_test.so")   # (a private directory: no clash with another user's build)
     subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O2", "-shared", "-fPIC", os.path.join(ROOT, "tools", "cu_thief.hip"), "-o", so])
     lib = ctypes.CDLL(so)
     lib.cu_thief_launch.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]

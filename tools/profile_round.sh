@@ -14,7 +14,7 @@ cd /tmp
 for wl in pretrain_step visual_fwd; do
   # clean, step-delimited traces: no divST pass, no parity model, no CPU baseline inside the traced process -> every per-step
   # kernel appears (warmup + steps + 1 per-kernel timing pass) = 8 (pretrain_step) / 14 (visual_fwd) times its per-step launch count
-  if [ $wl = pretrain_step ]; then ARGS="--steps 5 --warmup 2 --no-cpu-baseline --no-parity --no-divst"; B=B64; else ARGS="--workload visual_fwd --steps 10 --warmup 3 --no-cpu-baseline --no-parity --no-divst"; B=B32; fi
+  if [ $wl = pretrain_step ]; then ARGS="--full --steps 5 --warmup 2 --no-cpu-baseline --no-parity --no-divst"; B=B64; else ARGS="--full --workload visual_fwd --steps 10 --warmup 3 --no-cpu-baseline --no-parity --no-divst"; B=B32; fi
   rocprofv3 --kernel-trace --stats -d $O/trace_$wl -o t --output-format csv -- python $R/bench.py $ARGS > $O/trace_$wl.log 2>&1
   cp $(find $O/trace_$wl -name '*kernel_stats.csv' | head -1) $O/${wl}_${B}_kernel_stats.csv 2>/dev/null
   if [ $wl = visual_fwd ]; then continue; fi   # counters for the training step only (GPU-minute budget)
@@ -30,8 +30,8 @@ done
 # the passes above (copied into profiles/ here on the box; the same file comes home through gpurun_out/ and is committed under that name)
 cd $R
 cp $O/pretrain_step_B64_pmc_traffic.json profiles/${TAG}_pretrain_step_B64_pmc_traffic.json 2>/dev/null
-ALPRO_BENCH_SHAPES=1 python bench.py --steps 10 --warmup 3 > $O/bench_pretrain_step_B64.json 2> $O/gemm_shapes_pretrain_step_B64.txt
-ALPRO_BENCH_SHAPES=1 python bench.py --workload visual_fwd --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_visual_fwd_B32.json 2> $O/gemm_shapes_visual_fwd_B32.txt
+ALPRO_BENCH_SHAPES=1 python bench.py --full --steps 10 --warmup 3 > $O/bench_pretrain_step_B64.json 2> $O/gemm_shapes_pretrain_step_B64.txt
+ALPRO_BENCH_SHAPES=1 python bench.py --full --workload visual_fwd --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_visual_fwd_B32.json 2> $O/gemm_shapes_visual_fwd_B32.txt
 find $O -name '*.csv' -size +1500k -delete
 find $O -name '*.db' -delete
 du -sh $O; ls $O

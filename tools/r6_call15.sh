@@ -18,7 +18,7 @@ done
 cat $O/bert_bench.txt
 bash tools/ab_lib.sh 2>&1 | tee $O/ab_step.txt
 for t in 1 2 1 2; do
-  ALPRO_GEMM_TAIL=$t python bench.py --workload visual_fwd --steps 20 --warmup 5 --no-cpu-baseline --no-parity > $O/vfwd_tail$t.json 2>> $O/err.log
+  ALPRO_GEMM_TAIL=$t python bench.py --full --workload visual_fwd --steps 20 --warmup 5 --no-cpu-baseline --no-parity > $O/vfwd_tail$t.json 2>> $O/err.log
   python - $t <<'PY'
 import json, sys
 t = sys.argv[1]

@@ -7,7 +7,7 @@ mkdir -p $O
 cd /tmp
 for q in 4 8; do
 export GPU_MAX_HW_QUEUES=$q
-rocprofv3 --kernel-trace -d $O/trace$q -o t --output-format csv -- python $R/bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-parity --no-divst > $O/trace$q.log 2>&1
+rocprofv3 --kernel-trace -d $O/trace$q -o t --output-format csv -- python $R/bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --no-parity --no-divst > $O/trace$q.log 2>&1
 F=$(find $O/trace$q -name '*kernel_trace.csv' | head -1)
 echo "== GPU_MAX_HW_QUEUES=$q" >> $O/streams.txt
 python $R/tools/stream_report.py $F >> $O/streams.txt 2>&1

@@ -9,7 +9,7 @@ python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
 tail -2 $O/smoke.log
 ( time timeout 1500 python -m pytest tests -m gpu -x -q ) > $O/pytest_gpu.log 2>&1
 tail -4 $O/pytest_gpu.log
-python bench.py > $O/bench.json 2> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
 python - <<'PY'
 import json
 d = json.loads([x for x in open("gpurun_out/r6c33/bench.json") if x.startswith("{")][0])

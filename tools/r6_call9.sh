@@ -9,7 +9,7 @@ cd $R
 tail -5 $O/pytest_sched.log
 for cfg in "0 auto" "1 auto" "0 0" "1 0" "1 auto"; do
   set -- $cfg
-  ALPRO_DEFER_TEMPORAL_ADD=$1 ALPRO_SPLIT_STREAMS=$2 python bench.py --workload visual_fwd --steps 30 --warmup 5 --no-cpu-baseline --no-parity > $O/vfwd_defer$1_split$2.json 2>> $O/vfwd.err
+  ALPRO_DEFER_TEMPORAL_ADD=$1 ALPRO_SPLIT_STREAMS=$2 python bench.py --full --workload visual_fwd --steps 30 --warmup 5 --no-cpu-baseline --no-parity > $O/vfwd_defer$1_split$2.json 2>> $O/vfwd.err
   python - "$1" "$2" <<'PY'
 import json, sys
 d_, s = sys.argv[1:3]
