@@ -958,9 +958,10 @@ extern "C" int alpro_attn_fwd(const void* qkv, void* out, int dtype, int batch, 
   ALPRO_CHECK(!cls_q || (cls_out && cls_group > 0 && batch % cls_group == 0 && dtype != ALPRO_F32 && ((uintptr_t)cls_q % 16) == 0 && ((uintptr_t)cls_out % 16) == 0),
               "alpro_attn_fwd: the precise CLS query needs cls_out, a group size dividing the batch, 16-byte aligned fp32 side tensors and a 16-bit operand dtype");
   ALPRO_CHECK(qkv && out && batch > 0 && H > 0, "alpro_attn_fwd: bad args");
-  ALPRO_CHECK(L > 0 && L <= 256, "alpro_attn_fwd: L=%d unsupported (1..256; the path needs 40, 197, 237)", L);
+  ALPRO_CHECK(L > 0 && L <= ALPRO_ATTN_MAX_L, "alpro_attn_fwd: L=%d unsupported (1..%d = ALPRO_ATTN_MAX_L)", L, ALPRO_ATTN_MAX_L);
   ALPRO_CHECK(((uintptr_t)qkv % 16) == 0 && ((uintptr_t)out % 16) == 0, "alpro_attn_fwd: pointers must be 16-byte aligned");
   ALPRO_CHECK(!drop_seed || (drop_p > 0.f && drop_p < 1.f), "alpro_attn_fwd: dropout needs 0 < p < 1");
+  if (L > 256) return attn_long_fwd(qkv, out, dtype, batch, L, H, scale, key_bias, lse, drop_p, drop_seed, cls_q, cls_group, cls_out, (hipStream_t)stream);
   ALPRO_DISPATCH_DTYPE(dtype, T, return dispatch_attn<T>(qkv, out, batch, L, H, scale, key_bias, lse, drop_p, drop_seed, cls_q, cls_group, cls_out, (hipStream_t)stream));
   return ALPRO_OK;
 }

@@ -1500,7 +1500,8 @@ using namespace alpro;
 extern "C" int alpro_attn_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int dtype, int batch, int L,
                               int H, float scale, const float* key_bias, float drop_p, uint32_t drop_seed, void* stream) {
   ALPRO_CHECK(qkv && out && dout && lse && dqkv && batch > 0 && H > 0, "alpro_attn_bwd: bad args");
-  ALPRO_CHECK(L > 0 && L <= 256, "alpro_attn_bwd: L=%d unsupported (1..256)", L);
+  ALPRO_CHECK(L > 0 && L <= ALPRO_ATTN_MAX_L, "alpro_attn_bwd: L=%d unsupported (1..%d = ALPRO_ATTN_MAX_L)", L, ALPRO_ATTN_MAX_L);
+  if (L > 256) return attn_long_bwd(qkv, out, dout, lse, dqkv, dtype, batch, L, H, scale, key_bias, drop_p, drop_seed, (hipStream_t)stream);
   ALPRO_DISPATCH_DTYPE(dtype, T, return dispatch_bwd<T>(qkv, out, dout, lse, dqkv, batch, L, H, scale, key_bias, drop_p, drop_seed, (hipStream_t)stream));
   return ALPRO_OK;
 }

@@ -259,6 +259,11 @@ __device__ __forceinline__ uint32_t lds_addr_of(const void* p) { return (uint32_
 
 // ---- host side -----------------------------------------------------------------------------
 void set_error(const char* fmt, ...);
+// Attention over 256 < L <= ALPRO_ATTN_MAX_L (attention_long.hip): what alpro_attn_fwd / alpro_attn_bwd launch above the whole-row kernels.
+int attn_long_fwd(const void* qkv, void* out, int dtype, int batch, int L, int H, float scale, const float* key_bias, float* lse, float drop_p,
+                  uint32_t drop_seed, const float* cls_q, int cls_group, float* cls_out, hipStream_t st);
+int attn_long_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int dtype, int batch, int L, int H, float scale,
+                  const float* key_bias, float drop_p, uint32_t drop_seed, hipStream_t st);
 
 // Tuning knobs (measurement aids, not part of the arithmetic): initialised ONCE from the environment when the library is
 // loaded (ALPRO_GEMM_TILE / ALPRO_GEMM_GRID / ALPRO_GEMM_TUNE / ALPRO_TN_SPLITS), changed at run time only through

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define ALPRO_HIP_ABI_VERSION 20
+#define ALPRO_HIP_ABI_VERSION 21
 
 enum { ALPRO_OK = 0, ALPRO_ERR_INVALID = 1, ALPRO_ERR_LAUNCH = 2 };
 enum { ALPRO_F32 = 0, ALPRO_BF16 = 1, ALPRO_F16 = 2 };
@@ -224,15 +224,19 @@ int alpro_gemm_rows_f32(const float* A, int64_t lda, const float* W, int64_t ldw
                         const float* residual /* (M, ldr) or NULL */, int64_t ldr, const float* ln_gamma, const float* ln_beta, float ln_eps,
                         void* stream);
 
-/* Full (bidirectional) attention over `batch` sequences of L <= 256 tokens, head_dim 64:
+/* Full (bidirectional) attention over `batch` sequences of 1 <= L <= ALPRO_ATTN_MAX_L tokens, head_dim 64:
  * spatial half of divided attention (vit.py:180 on (B*T, 1+N) tokens, :81-96) and the BERT
  * text / fusion self-attention (xbert.py:299-341) where key_bias (batch, L) is the additive
- * (1 - mask) * -10000 of xbert.py:936-937 (NULL = no mask).  K/V of one (sequence, head) stay
- * resident in LDS; QK^T and PV run on MFMA; softmax in fp32 registers.  lse (batch, H, L) optional. */
+ * (1 - mask) * -10000 of xbert.py:936-937 (NULL = no mask).  L <= 256: K/V of one (sequence, head) stay
+ * resident in LDS; L > 256 (ABI 21: long captions, fusion over caption + 197 video tokens): K/V stream through LDS
+ * in 64-key blocks with an online softmax (attention_long.hip), same contract -- lse layout, dropout mask, cls_q.
+ * QK^T and PV run on MFMA; softmax in fp32 registers.  lse (batch, H, L) optional. */
+#define ALPRO_ATTN_MAX_L 1024
 int alpro_attn_fwd(const void* qkv, void* out, int dtype, int batch, int L, int H, float scale,
                    const float* key_bias, float* lse, float drop_p, uint32_t drop_seed,
                    /* round 4, precise CLS query fused into the same launch (NULL = off; semantics of alpro_attn_cls_fwd with K / V taken from the
-                    * images already staged in LDS): cls_q (batch / cls_group, 3*H*64) fp32, cls_out (batch, H*64) fp32; 16-bit dtypes only */
+                    * images already staged in LDS): cls_q (batch / cls_group, 3*H*64) fp32, cls_out (batch, H*64) fp32; 16-bit dtypes only.
+                    * Only the q third of cls_q is read; every key's K / V, the CLS token's included, is the 16-bit one of qkv */
                    const float* cls_q, int cls_group, float* cls_out, void* stream);
 /* drop_p > 0: dropout on the attention probabilities (xbert.py:331), mask = hash(seed, ((b*H+h)*L+q)*L+key). */
 
@@ -283,7 +287,8 @@ int alpro_cast_from_f32(const float* src, void* dst, int dtype, int64_t n, void*
  * run_pretrain_sparse.py:599 through vit.py:136-213 and xbert.py:457-519) --------------------------------- */
 
 /* dQKV (rows, 3*H*64) from dO (rows, H*64), the saved qkv / out and the row log-sum-exp of the forward.
- * P is recomputed on MFMA; delta = rowsum(dO o O); see attention_bwd.hip. */
+ * P is recomputed on MFMA; delta = rowsum(dO o O); see attention_bwd.hip (L <= 256) and attention_long.hip
+ * (256 < L <= ALPRO_ATTN_MAX_L: a dQ and a dK/dV launch, no atomics, no workspace). */
 int alpro_attn_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int dtype,
                    int batch, int L, int H, float scale, const float* key_bias, float drop_p, uint32_t drop_seed,
                    void* stream);
