@@ -4,7 +4,7 @@ import math
 import pytest
 import torch
 
-from tests.test_hip_ops import DTYPES, _hip, close, rnd
+from tests.test_hip_ops import DTYPES, _hip, check_attn_fwd, close, logit_rel_err, rnd
 
 pytestmark = pytest.mark.gpu
 
@@ -22,9 +22,65 @@ def attn_ref(qkv, batch, L, H, scale, bias=None, group=None):
     return (s.softmax(-1) @ t[2]).transpose(1, 2).reshape(batch * L, H * 64)
 
 
+def check_attn_bwd(dt, batch, L, H, regime, mask, seed, drop_p=0.0, kind=None):
+    """alpro_attn_fwd + alpro_attn_bwd (option attn_bwd = kind if given) on attn_inputs against fp64 autograd.  The gradients' scale is not
+    O(1) in every regime (peaked: |dQ|, |dK| ~ 3x; late_max: dV of the dominant key sums dO over all queries), so atol is multiplied by
+    max(1, max|ref|) of each tensor.  fp32: plus 2 d x the gradient's sum of absolute terms -- every gradient is a sum of products of at most
+    two p's (dV = P^T dO, dS = P o (dO V^T - rowsum(P o dO V^T)), dQ = scale dS K, dK = scale dS^T Q), so a relative error d on every p
+    (test_hip_ops.logit_rel_err) moves it by at most 2 d times the same sums over absolute values.  The reference takes
+    delta = rowsum(dO o O) from `out` as alpro_attn_bwd receives it (stored in dt) -- the backward's contract, dS = P o (dP - delta) -- where
+    autograd has rowsum(P o dP) of the exact O: where |K| is large and dS vanishes (late_max with dropout: O = v* / (1 - p) is off the grid,
+    K* = 32, the exact dQ ~ 0) the two differ by ~0.35 in bf16, the formulation's difference and not a kernel error."""
+    hip = _hip()
+    qkv, bias, out, lse = check_attn_fwd(dt, batch, L, H, regime, mask, seed, drop_p)
+    dout = rnd(batch * L, H * 64, seed=seed + 1).to(dt)
+    dseed = 1000 + seed if drop_p else 0
+    q64 = qkv.double().requires_grad_(True)
+    t = q64.view(batch, L, 3, H, 64).permute(2, 0, 3, 1, 4)
+    s = (t[0] @ t[1].transpose(-1, -2)) * 0.125
+    if bias is not None:
+        s = s + bias[:, None, None, :].double()
+    sm = s.softmax(-1)
+    pr = sm
+    if drop_p:
+        pr = pr * _keep_mask(dseed, batch * H * L * L, drop_p).view(batch, H, L, L).double() / (1.0 - drop_p)
+    o64 = pr @ t[2]
+    o64.transpose(1, 2).reshape(batch * L, H * 64).backward(dout.double())
+    kb = None if bias is None else bias.cuda()
+    if kind is None:
+        dqkv = hip.attn_bwd(qkv.cuda(), out, dout.cuda(), lse, batch, L, H, 0.125, kb, drop_p=drop_p, drop_seed=dseed)
+    else:
+        with hip.option("attn_bwd", kind):
+            dqkv = hip.attn_bwd(qkv.cuda(), out, dout.cuda(), lse, batch, L, H, 0.125, kb, drop_p=drop_p, drop_seed=dseed)
+    g = q64.grad.view(batch * L, 3, H * 64)
+    d = dqkv.view(batch * L, 3, H * 64)
+    extra = [0.0] * 3
+    rel = logit_rel_err(dt, qkv, bias, batch, L, H)
+    with torch.no_grad():
+        t64 = qkv.double().view(batch, L, 3, H, 64).permute(2, 0, 3, 1, 4)
+        do64 = dout.double().view(batch, L, H, 64).transpose(1, 2)
+        dds = sm.detach() * (do64 * (out.detach().cpu().double().view(batch, L, H, 64).transpose(1, 2) - o64.detach())).sum(-1, keepdim=True)
+        g = g.clone()
+        g[:, 0] -= (0.125 * dds @ t64[1]).transpose(1, 2).reshape(batch * L, H * 64)
+        g[:, 1] -= (0.125 * dds.transpose(-1, -2) @ t64[0]).transpose(1, 2).reshape(batch * L, H * 64)
+        if rel:
+            a = t64.abs()
+            p, ado = pr.detach(), do64.abs()
+            adp = ado @ a[2].transpose(-1, -2)
+            ads = p * (adp + (p * adp).sum(-1, keepdim=True))
+            extra = [e + 2 * rel * float(x.abs().max())
+                     for e, x in zip(extra, (0.125 * ads @ a[1], 0.125 * ads.transpose(-1, -2) @ a[0], p.transpose(-1, -2) @ ado))]
+    rtol, atol = GRAD_TOL[dt]
+    for i, name in enumerate("QKV"):
+        ref = g[:, i]
+        close(d[:, i], ref, rtol, atol * max(1.0, float(ref.abs().max())) + extra[i], "d%s %s L=%d H=%d %s/%s" % (name, dt, L, H, regime, mask))
+
+
 @pytest.mark.parametrize("dt", DTYPES)
 @pytest.mark.parametrize("batch,L,masked", [(2, 40, True), (2, 197, False), (1, 237, True), (1, 70, False), (1, 130, False), (2, 161, True),
-                                            (1, 192, False), (1, 225, False), (2, 256, True)])
+                                            (1, 192, False), (1, 225, False), (2, 256, True),
+                                            (2, 1, False), (2, 2, False), (2, 31, True), (2, 33, True), (1, 64, False), (2, 65, True),
+                                            (2, 96, True), (1, 97, False), (2, 128, True), (1, 129, False), (2, 224, True), (2, 255, True)])
 def test_attn_bwd(dt, batch, L, masked):
     hip = _hip()
     H = 12
@@ -48,7 +104,7 @@ def test_attn_bwd(dt, batch, L, masked):
 
 
 @pytest.mark.parametrize("dt", DTYPES)
-@pytest.mark.parametrize("T,groups", [(8, 9), (4, 17), (2, 48), (16, 3)])
+@pytest.mark.parametrize("T,groups", [(8, 9), (4, 17), (2, 48), (16, 3), (1, 40), (32, 3)])
 def test_attn_temporal_bwd(dt, T, groups):
     hip = _hip()
     H = 12
@@ -60,6 +116,39 @@ def test_attn_temporal_bwd(dt, T, groups):
     out, lse = hip.attn_temporal(qkv.cuda(), T, H, 0.125, want_lse=True)
     dqkv = hip.attn_temporal_bwd(qkv.cuda(), out, dout.cuda(), lse, T, H, 0.125)
     close(dqkv, q64.grad, *GRAD_TOL[dt], "temporal dqkv")
+
+
+# (batch, L, H, regime, mask): the stress regimes x masks through the whole-row backward (two-phase below 5 key tiles, the default choice
+# above), both sides of the nkt buckets, one and 16 heads
+ATTN_STRESS_BWD_SHORT = ([(2, L, 12, r, m) for L in (33, 129, 256) for r in ("peaked", "late_max", "offset") for m in ("fusion", "single")]
+                         + [(4, 197, 12, "early_max", "fusion"), (2, 97, 12, "peaked", "all"), (2, 97, 12, "gauss", "all"), (2, 65, 1, "peaked", "fusion"),
+                            (2, 225, 16, "late_max", "fusion"), (2, 2, 12, "offset", "tail")])
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("batch,L,H,regime,mask", ATTN_STRESS_BWD_SHORT)
+def test_attn_stress_bwd(dt, batch, L, H, regime, mask):
+    check_attn_bwd(dt, batch, L, H, regime, mask, seed=3 * L + H)
+
+
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("kind", [0, 1, 2])
+@pytest.mark.parametrize("batch,L,regime,p", [(4, 150, "peaked", 0.0), (4, 200, "late_max", 0.0), (4, 240, "peaked", 0.0), (2, 129, "offset", 0.0),
+                                              (4, 200, "peaked", 0.1)])
+def test_attn_bwd_kinds_vs_fp64(dt, kind, batch, L, regime, p):
+    """Every choice of option attn_bwd (0 two-phase, 1 per-shape default, 2 key-owned wherever >= 5 key tiles) at 5, 7 and 8 key tiles under
+    the fusion mask, with and without dropout, against fp64 (test_attn_bwd_key_owned_vs_two_phase compares the kinds with each other)."""
+    check_attn_bwd(dt, batch, L, 12, regime, "fusion", seed=17 * L + kind, drop_p=p, kind=kind)
+
+
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("batch,L,regime,mask", [(4, 33, "peaked", "fusion"), (2, 31, "peaked", "none"), (2, 97, "late_max", "fusion"),
+                                                 (4, 129, "peaked", "fusion"), (2, 200, "peaked", "none"), (2, 240, "late_max", "fusion"),
+                                                 (4, 385, "peaked", "fusion"), (2, 1024, "late_max", "fusion")])
+def test_attn_dropout_fusion_mask(dt, batch, L, regime, mask):
+    """Attention-probability dropout (p = 0.1) under the fusion mask (and, for the instances without HAS_BIAS, no mask), forward and backward
+    against fp64 with the same keep mask, in every nkt bucket of the whole-row kernels and on the long path."""
+    check_attn_bwd(dt, batch, L, 12, regime, mask, seed=23 * L, drop_p=0.1)
 
 
 @pytest.mark.parametrize("dt", DTYPES)

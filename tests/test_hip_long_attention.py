@@ -5,8 +5,8 @@ import hashlib
 import pytest
 import torch
 
-from tests.test_hip_bwd_ops import GRAD_TOL, _keep_mask, attn_ref
-from tests.test_hip_ops import DTYPES, _hip, close, ref_attention, rnd
+from tests.test_hip_bwd_ops import GRAD_TOL, _keep_mask, attn_ref, check_attn_bwd
+from tests.test_hip_ops import DTYPES, _hip, check_attn_fwd, close, ref_attention, rnd
 
 pytestmark = pytest.mark.gpu
 
@@ -24,7 +24,9 @@ def _bias(batch, L, seed):
 
 
 FWD_CASES = [(2, 257, False), (2, 293, False), (2, 320, True), (1, 511, False), (1, 512, False), (2, 513, False), (2, 517, True),
-             (1, 709, False), (1, 1024, False)]
+             (1, 709, False), (1, 1024, False),
+             # last key block of 1 / 32 / 33 / 63 / 64 keys; exact and ragged 128-query workgroups; the bound, masked, two sequences
+             (2, 257, True), (2, 288, True), (2, 289, True), (1, 319, True), (1, 384, True), (2, 385, True), (2, 1023, True), (2, 1024, True)]
 
 
 @pytest.mark.parametrize("dt", DTYPES)
@@ -40,7 +42,9 @@ def test_long_attn_fwd(dt, batch, L, masked):
 
 
 @pytest.mark.parametrize("dt", DTYPES)
-@pytest.mark.parametrize("batch,L,masked", [(2, 257, False), (2, 320, True), (1, 513, False), (2, 517, True), (1, 709, False)])
+@pytest.mark.parametrize("batch,L,masked", [(2, 257, False), (2, 320, True), (1, 513, False), (2, 517, True), (1, 709, False),
+                                            (2, 288, True), (2, 289, False), (1, 319, True), (2, 384, True), (1, 385, False), (1, 1023, True),
+                                            (1, 1024, False)])
 def test_long_attn_bwd(dt, batch, L, masked):
     hip = _hip()
     qkv = (rnd(batch * L, 3 * H * 64, seed=600 + L) * 0.7).to(dt)
@@ -55,6 +59,29 @@ def test_long_attn_bwd(dt, batch, L, masked):
     d = dqkv.view(batch * L, 3, H * 64)
     for i, name in enumerate("QKV"):
         close(d[:, i], g[:, i], *GRAD_TOL[dt], "long d%s" % name)
+
+
+# (batch, L, H, regime, mask) for the key-blocked path: the stress regimes x the fusion mask (a fully masked 64-key block between valid ones at
+# L = 385 / 1024 for the sequences that keep 1 or 2 text keys) and the single mask; one head (grid 3 / 4 workgroups, no XCD remap) and 16 heads
+# (grid 2 * 16 * 4 = 128, remapped); H = 12, batch 2: grids 72 / 96 / 192 (remapped)
+ATTN_STRESS_LONG = ([(2, L, 12, r, m) for L in (289, 385, 1024) for r in ("peaked", "late_max", "offset") for m in ("fusion", "single")]
+                    + [(4, 320, 12, "gauss", "fusion"), (2, 1023, 12, "early_max", "fusion"), (2, 257, 12, "late_max", "tail"), (2, 319, 12, "gauss", "all"),
+                       (2, 319, 12, "offset", "all"), (2, 384, 12, "late_max", "none"), (1, 289, 1, "peaked", "fusion"), (2, 385, 16, "late_max", "fusion")])
+ATTN_STRESS_BWD_LONG = ([(2, 385, 12, r, m) for r in ("peaked", "late_max", "offset") for m in ("fusion", "single")]
+                        + [(2, 1023, 12, "late_max", "fusion"), (2, 1024, 12, "peaked", "single"), (2, 1024, 12, "offset", "fusion"),
+                           (2, 319, 12, "gauss", "all"), (1, 385, 1, "peaked", "fusion"), (2, 289, 16, "late_max", "fusion")])
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("batch,L,H,regime,mask", ATTN_STRESS_LONG)
+def test_long_attn_stress_fwd(dt, batch, L, H, regime, mask):
+    check_attn_fwd(dt, batch, L, H, regime, mask, seed=L + 7 * H)
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("batch,L,H,regime,mask", ATTN_STRESS_BWD_LONG)
+def test_long_attn_stress_bwd(dt, batch, L, H, regime, mask):
+    check_attn_bwd(dt, batch, L, H, regime, mask, seed=5 * L + H)
 
 
 @pytest.mark.parametrize("dt", DTYPES)

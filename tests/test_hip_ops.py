@@ -336,8 +336,137 @@ def ref_attention(qkv, batch, L, H, scale, bias=None, group=None):
     return (p @ t[2]).transpose(1, 2).reshape(batch * L, H * 64), torch.logsumexp(s, -1)
 
 
+# Stress inputs for the attention family (also imported by test_hip_bwd_ops, test_hip_long_attention and the CPU self-check in
+# test_host_cpu).  Every value lies on a grid of 2^-5 (2^-3 for the peaked q / k) below 8 (16) in magnitude: exact in bf16 AND f16, so
+# .to(dt) is lossless for all three dtypes, and every q.k product sum is exact in fp32 whatever the summation order.
+ATTN_REGIMES = ("gauss", "peaked", "late_max", "early_max", "offset")
+ATTN_MASKS = ("none", "tail", "fusion", "single", "all")
+FWD_TOL = {torch.float32: (2e-5, 2e-5), torch.bfloat16: (2e-2, 2e-2), torch.float16: (3e-3, 3e-3)}   # P and O are rounded to dt
+OFFSET_C = 13.75   # offset: q[:4] = k[:4] = 13.75 lifts every score by 0.125 * 4 * 13.75^2 = 94.53
+DOM_Q, DOM_K = 8.0, 32.0   # late_max / early_max: q[:4] = 8, k*[:4] = 32, k*[4:] = 0 -> key k* scores 0.125 * 4 * 8 * 32 = 128 (other keys ~N(0, 1))
+
+
+def _on_grid(x, step, lim):
+    return torch.round(x.clamp(-lim, lim) / step) * step
+
+
+def attn_mask(batch, L, kind, seed=0):
+    """(batch, L) {0, 1} key mask, a different one per sequence.  fusion: cat(text, ones(Lv)) as alpro_models.py builds the fusion encoder's
+    mask -- the padded caption keys sit in the MIDDLE of the sequence, followed by Lv valid video keys (Lv = 197 above L = 197, else L // 2);
+    sequence b keeps (1, 2, Lt // 2, Lt)[(b + seed) % 4] text keys."""
+    m = torch.ones(batch, L)
+    if kind == "tail":
+        for b in range(batch):
+            m[b, L - min(L - 1, 1 + (3 + 7 * b + seed) % max(1, L // 3)):] = 0
+    elif kind == "fusion":
+        lt = L - (197 if L > 197 else L // 2)
+        for b in range(batch):
+            m[b, max(1, (1, 2, lt // 2, lt)[(b + seed) % 4]):lt] = 0
+    elif kind == "single":
+        m[:, 1:] = 0
+    elif kind == "all":
+        m[:] = 0
+    else:
+        assert kind == "none", kind
+    return m
+
+
+def attn_inputs(batch, L, H, regime="gauss", mask="none", seed=0):
+    """-> qkv (batch*L, 3*H*64) fp32, exact in bf16 and f16; key bias (batch, L) = (1 - m) * -10000 as xbert.key_bias builds it (None for "none").
+    gauss: N(0, 1) q / k / v.  peaked: q, k with std 4 (score std 16: the median row puts > 0.95 on its top
+    key up to L = 1024; std 3, score std 9, gives only 0.83 at L = 256).  late_max / early_max: per sequence one valid key -- the LAST valid key
+    (in the last 64-key block and 32-key tile whenever the mask keeps the sequence's last key) / key 0 -- scores >= 120 above every other key,
+    for every query and head.  offset: every score lifted by 90..100 (a softmax that does not subtract the row max overflows fp32 exp)."""
+    assert regime in ATTN_REGIMES, regime
+    g = torch.Generator().manual_seed(seed)
+    t = _on_grid(torch.randn(batch, L, 3, H, 64, generator=g), 2.0 ** -5, 7.96875)
+    m = attn_mask(batch, L, mask, seed)
+    if regime == "peaked":
+        t[:, :, :2] = _on_grid(4.0 * torch.randn(batch, L, 2, H, 64, generator=g), 2.0 ** -3, 15.875)
+    elif regime == "offset":
+        t[:, :, :2, :, :4] = OFFSET_C
+    elif regime in ("late_max", "early_max"):
+        t[:, :, 0, :, :4] = DOM_Q
+        t[:, :, 1, :, :4] = 0.0
+        for b in range(batch):
+            j = int(m[b].nonzero().max()) if regime == "late_max" and m[b].any() else 0
+            t[b, j, 1, :, :4] = DOM_K
+            t[b, j, 1, :, 4:] = 0.0
+    bias = None if mask == "none" else (1.0 - m) * -10000.0
+    return t.reshape(batch * L, 3 * H * 64).contiguous(), bias
+
+
+def logit_rel_err(dt, qkv, bias, batch, L, H, scale=0.125):
+    """-> d, a bound on the relative error of every p (fp32 only).  The kernels form every logit in the log2 domain in fp32,
+    x = fma(s, scale * log2(e), bias * log2(e)); s itself is exact here (attn_inputs' grids).  With |x| < 2^e the rounding leaves at most
+    2^(e-24) on x (one ulp, the exp2 approximation included); the row max is subtracted exactly (Sterbenz) and its own rounding cancels
+    between numerator and normaliser, so every p = 2^(x - max) / l is off by a factor within 1 +- d, d = ln(2) * 2^(e-24), and
+    out = sum p v / sum p by at most 2 d max|v|.  Benign scores (|x| < 16): d = 6.6e-7.  Offset scores (x ~ 137, e = 8): d = 1.1e-5.
+    Every key masked (x ~ -10000 * log2(e) = -14427, e = 14, where fp32 values are 2^-10 apart): d = 6.8e-4 -- the model's own fp32
+    arithmetic (scores + bias, then softmax) loses the same.  A masked key next to a valid one has p = 2^-14000 = 0, so only the valid keys'
+    logits count unless the whole sequence is masked.  16-bit dtypes: P is rounded to dt (2^-8 / 2^-11 relative), FWD_TOL / GRAD_TOL cover it."""
+    if dt != torch.float32:
+        return 0.0
+    t = qkv.double().view(batch, L, 3, H, 64)
+    s = torch.einsum("bqhd,bkhd->bhqk", t[:, :, 0], t[:, :, 1]) * scale
+    if bias is not None:
+        b = bias.double()[:, None, None, :]
+        s = torch.where((bias < 0).all(-1)[:, None, None, None], s + b, s.masked_fill(b < 0, 0.0))
+    x = float(s.abs().max()) * math.log2(math.e)
+    return math.log(2.0) * 2.0 ** (math.frexp(x)[1] - 24)
+
+
+def logit_atol(dt, qkv, bias, batch, L, H, scale=0.125):
+    """The forward's share of logit_rel_err: 2 d max|v|."""
+    d = logit_rel_err(dt, qkv, bias, batch, L, H, scale)
+    return 2.0 * d * float(qkv.double().view(batch, L, 3, H, 64)[:, :, 2].abs().max()) if d else 0.0
+
+
+def check_attn_fwd(dt, batch, L, H, regime, mask, seed, drop_p=0.0):
+    """alpro_attn_fwd on attn_inputs against fp64 (every row, padded queries included) -> (qkv, bias, out, lse) for the backward."""
+    hip = _hip()
+    qkv, bias = attn_inputs(batch, L, H, regime, mask, seed)
+    qkv = qkv.to(dt)
+    kb = None if bias is None else bias.cuda()
+    dseed = 1000 + seed if drop_p else 0
+    out, lse = hip.attn(qkv.cuda(), batch, L, H, 0.125, kb, want_lse=True, drop_p=drop_p, drop_seed=dseed)
+    keep = None
+    if drop_p:
+        from tests.test_hip_bwd_ops import _keep_mask
+        keep = _keep_mask(dseed, batch * H * L * L, drop_p).view(batch, H, L, L).double()
+    t = qkv.double().view(batch, L, 3, H, 64).permute(2, 0, 3, 1, 4)
+    s = (t[0] @ t[1].transpose(-1, -2)) * 0.125
+    if bias is not None:
+        s = s + bias[:, None, None, :].double()
+    p = s.softmax(-1) if keep is None else s.softmax(-1) * keep / (1.0 - drop_p)
+    ref = (p @ t[2]).transpose(1, 2).reshape(batch * L, H * 64)
+    rtol, atol = FWD_TOL[dt]
+    what = "%s L=%d H=%d %s/%s" % (dt, L, H, regime, mask)
+    close(out, ref, rtol, atol + logit_atol(dt, qkv, bias, batch, L, H), "attn out " + what)
+    close(lse, torch.logsumexp(s, -1), 1e-5, 1e-4, "attn lse " + what)
+    return qkv, bias, out, lse
+
+
+# (batch, L, H, regime, mask): both edges of the whole-row nkt buckets (<= 2, <= 4, <= 7, 8 key tiles), a fully masked 32-key tile between
+# valid ones (fusion at L = 129 / 197), every regime x mask, one and 16 heads
+ATTN_STRESS_SHORT = ([(2, L, 12, r, m) for L in (33, 129, 256) for r in ("peaked", "late_max", "offset") for m in ("fusion", "single")]
+                     + [(4, 197, 12, r, "fusion") for r in ("gauss", "early_max")]
+                     + [(2, 97, 12, r, m) for r, m in (("gauss", "all"), ("peaked", "all"), ("offset", "all"), ("late_max", "tail"),
+                                                       ("early_max", "none"), ("offset", "none"))]
+                     + [(3, 65, 1, "peaked", "fusion"), (2, 225, 16, "late_max", "fusion"), (1, 1, 12, "offset", "none"), (2, 2, 12, "peaked", "fusion")])
+
+
 @pytest.mark.parametrize("dt", DTYPES)
-@pytest.mark.parametrize("batch,L,masked", [(3, 40, True), (2, 197, False), (2, 237, True), (1, 100, False), (2, 256, False)])
+@pytest.mark.parametrize("batch,L,H,regime,mask", ATTN_STRESS_SHORT)
+def test_attn_stress_fwd(dt, batch, L, H, regime, mask):
+    check_attn_fwd(dt, batch, L, H, regime, mask, seed=L + 7 * H + 31 * ATTN_REGIMES.index(regime))
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("batch,L,masked", [(3, 40, True), (2, 197, False), (2, 237, True), (1, 100, False), (2, 256, False),
+                                            (2, 1, False), (2, 2, False), (2, 31, True), (2, 33, True), (1, 64, False), (2, 65, True),
+                                            (2, 96, True), (1, 97, False), (2, 128, True), (1, 129, False), (2, 224, True), (1, 225, False),
+                                            (2, 255, True)])
 def test_attn_full(dt, batch, L, masked):
     hip = _hip()
     H = 12
@@ -356,16 +485,24 @@ def test_attn_full(dt, batch, L, masked):
 
 
 @pytest.mark.parametrize("dt", DTYPES)
-@pytest.mark.parametrize("T,groups", [(8, 11), (4, 17), (2, 5), (16, 3), (8, 64)])
+@pytest.mark.parametrize("T,groups", [(8, 11), (4, 17), (2, 5), (16, 3), (8, 64), (1, 40), (32, 3)])
 def test_attn_temporal(dt, T, groups):
     hip = _hip()
     H = 12
     rows = groups * T
     qkv = rnd(rows, 3 * H * 64, seed=60 + T).to(dt)
     out = hip.attn_temporal(qkv.cuda(), T, H, 0.125)
-    ref, _ = ref_attention(qkv.double(), groups, T, H, 0.125)
+    ref, ref_lse = ref_attention(qkv.double(), groups, T, H, 0.125)
     tol = {torch.float32: (2e-5, 2e-5), torch.bfloat16: (2e-2, 2e-2), torch.float16: (3e-3, 3e-3)}[dt]
     close(out, ref, *tol, "temporal attn")
+    out2, lse = hip.attn_temporal(qkv.cuda(), T, H, 0.125, want_lse=True)
+    assert torch.equal(out2, out)
+    close(temporal_lse_rows(lse, rows, H), ref_lse.permute(0, 2, 1).reshape(rows, H), 1e-5, 1e-4, "temporal lse vs fp64")
+
+
+def temporal_lse_rows(lse, rows, H):
+    """alpro_attn_temporal_fwd's lse ((rows + 31) // 32, H, 32): row c * 32 + r of head h at [c, h, r] -> (rows, H)."""
+    return lse.detach().cpu().permute(0, 2, 1).reshape(-1, H)[:rows]
 
 
 @pytest.mark.parametrize("dt", [torch.float16, torch.bfloat16])
@@ -610,7 +747,7 @@ def test_gemm_tile_scheduler_with_compute_units_taken(stolen):
 
 @pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("batch,L,group,masked,p", [(6, 197, 3, False, 0.0), (4, 40, 1, True, 0.0), (8, 30, 1, True, 0.1), (2, 5, 2, False, 0.0), (16, 197, 8, False, 0.0),
-                                                    (3, 256, 1, True, 0.0)])
+                                                    (3, 256, 1, True, 0.0), (2, 100, 1, False, 0.0), (4, 97, 1, True, 0.0), (2, 256, 1, False, 0.0)])
 def test_attn_cls_precise_query(dt, batch, L, group, masked, p):
     """The CLS query's attention in fp32 (round 4) against fp64, in both forms: alpro_attn_cls_fwd (stand-alone: q and the CLS token's own
     k / v unrounded from the fp32 side tensor, one row per `group` sequences; the other tokens' K / V from the 16-bit qkv tensor) and the
@@ -652,6 +789,42 @@ def test_attn_cls_precise_query(dt, batch, L, group, masked, p):
             pr = pr * keep / (1.0 - p)
         ref = torch.einsum("bhl,blhd->bhd", pr, v).reshape(batch, H * 64)
         close(got, ref, 2e-5, 2e-5, "attn_cls " + name)
+
+
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("batch,L,p", [(4, 129, 0.0), (4, 197, 0.1), (2, 256, 0.0), (4, 385, 0.0), (2, 1023, 0.1)])
+def test_attn_cls_precise_query_fusion_late_max(dt, batch, L, p):
+    """The precise [CLS] query -- alpro_attn_cls_fwd and the cls_q side path of alpro_attn_fwd (whole-row kernels at L <= 256, the companion
+    launch of the long path above) -- under the fusion mask (padded caption keys in the middle, a fully masked 32-key tile at L = 129 / 197,
+    a fully masked 64-key block at L = 385) with the late_max scores: the CLS query's q has the dominant component, so each sequence's
+    last key beats every other by >= 120.  cls_q is the CLS row off its grid by up to 1e-3 (the unrounded fp32 row)."""
+    hip = _hip()
+    H = 12
+    qkv, bias = attn_inputs(batch, L, H, "late_max", "fusion", seed=900 + L)
+    qkv = qkv.to(dt)
+    g = torch.Generator().manual_seed(901 + L)
+    cls = qkv.float().view(batch, L, 3 * H * 64)[:, 0] + 1e-3 * (torch.rand(batch, 3 * H * 64, generator=g) - 0.5)
+    seed = 555 if p > 0 else 0
+    kb = bias.cuda()
+    out = hip.attn_cls(qkv.cuda(), cls.cuda(), batch, L, H, 0.125, group=1, key_bias=kb, drop_p=p, drop_seed=seed)
+    plain = hip.attn(qkv.cuda(), batch, L, H, 0.125, kb, drop_p=p, drop_seed=seed)
+    full, fused = hip.attn(qkv.cuda(), batch, L, H, 0.125, kb, drop_p=p, drop_seed=seed, cls_q=cls.cuda(), cls_group=1)
+    assert torch.equal(full, plain)
+    keep = None
+    if p > 0:
+        from tests.test_hip_bwd_ops import _keep_mask
+        keep = _keep_mask(seed, batch * H * L * L, p).view(batch, H, L, L)[:, :, 0].double()
+    for name, got, own_kv in (("stand-alone", out, True), ("fused", fused, False)):
+        t = qkv.double().view(batch, L, 3, H, 64).clone()
+        c = cls.double().view(batch, 3, H, 64)
+        if own_kv:
+            t[:, 0] = c
+        sc = torch.einsum("bhd,blhd->bhl", c[:, 0], t[:, :, 1]) * 0.125 + bias[:, None, :].double()
+        pr = sc.softmax(-1)
+        if keep is not None:
+            pr = pr * keep / (1.0 - p)
+        ref = torch.einsum("bhl,blhd->bhd", pr, t[:, :, 2]).reshape(batch, H * 64)
+        close(got, ref, 2e-5, 2e-5, "attn_cls %s L=%d" % (name, L))
 
 
 @pytest.mark.gpu

@@ -1440,3 +1440,121 @@ def test_round6_forward_schedule_switches(monkeypatch):
         rt.set_wgrad_stream(prev_w)
     from alpro_amd import hip
     assert "alpro_add_layernorm_pre_mlp2" in hip.EXPORTS and "alpro_adamw_step_lp" in hip.EXPORTS
+
+
+# ------------------------------------------------------------------------------------------------ attention stress inputs (CPU self-check)
+def _online_softmax_attn(qkv, batch, L, H, scale, bias=None, fault=None):
+    """fp32 restatement of attn_long_fwd_kernel's key loop (attention_long.hip): 64-key blocks of two 32-key tiles, log2-domain logits
+    x = s * scale * log2(e) + bias * log2(e) (-inf past L), running max m and sum l per query, o and l rescaled by alpha = 2^(m - m_new).
+    fault plants one bug: "o_stale" (o not rescaled when the max rises), "l_stale" (l not rescaled), "tile_max" (the block max over its
+    first 32-key tile only), "prev_bias" (each block reads the key bias of the block before it).  -> out (batch*L, H*64), lse (batch, H, L)."""
+    f32 = torch.float32
+    t = qkv.to(f32).view(batch, L, 3, H, 64).permute(2, 0, 3, 1, 4)
+    q, k, v = t[0], t[1], t[2]
+    log2e = torch.tensor(1.4426950408889634, dtype=f32)
+    sl = torch.tensor(scale, dtype=f32) * log2e
+    nkb = (L + 63) // 64
+    bb = torch.full((batch, nkb * 64), float("-inf"), dtype=f32)
+    bb[:, :L] = 0.0 if bias is None else bias.to(f32) * log2e
+    m = torch.full((batch, H, L), float("-inf"), dtype=f32)
+    l = torch.zeros(batch, H, L, dtype=f32)
+    o = torch.zeros(batch, H, L, 64, dtype=f32)
+    for kb in range(nkb):
+        lo, hi = kb * 64, min(L, kb * 64 + 64)
+        src = kb - 1 if fault == "prev_bias" and kb > 0 else kb
+        x = (q @ k[:, :, lo:hi].transpose(-1, -2)) * sl + bb[:, None, None, src * 64:src * 64 + hi - lo]
+        mb = (x[..., :32] if fault == "tile_max" else x).amax(-1)
+        mn = torch.maximum(m, mb)
+        alpha = torch.exp2(m - mn)
+        p = torch.exp2(x - mn[..., None])
+        l = (l if fault == "l_stale" else l * alpha) + p.sum(-1)
+        o = (o if fault == "o_stale" else o * alpha[..., None]) + p @ v[:, :, lo:hi]
+        m = mn
+    out = (o / l[..., None]).transpose(1, 2).reshape(batch * L, H * 64)
+    return out, (m + torch.log2(l)) * torch.tensor(0.6931471805599453, dtype=f32)
+
+
+ATTN_FAULTS = ("o_stale", "l_stale", "tile_max", "prev_bias")
+
+
+def _emulator_errors(batch, L, H, regime, mask, seed, fault):
+    """-> (max err / allowed) of the emulator's out against fp64, at the fp32 forward tolerance (test_hip_ops.FWD_TOL + logit_atol)."""
+    from tests.test_hip_ops import FWD_TOL, attn_inputs, logit_atol, ref_attention
+    qkv, bias = attn_inputs(batch, L, H, regime, mask, seed)
+    out, _ = _online_softmax_attn(qkv, batch, L, H, 0.125, bias, fault)
+    ref, _ = ref_attention(qkv.double(), batch, L, H, 0.125, bias)
+    rtol, atol = FWD_TOL[torch.float32]
+    allowed = atol + logit_atol(torch.float32, qkv, bias, batch, L, H) + rtol * ref.abs()
+    err = (out.double() - ref).abs()
+    return float("inf") if not torch.isfinite(out).all() else float((err / allowed).max())
+
+
+def test_attention_stress_regimes_do_what_they_claim():
+    """The inputs of the attention stress tests (test_hip_ops.attn_inputs / attn_mask) have the properties their names promise."""
+    from tests.test_hip_ops import ATTN_MASKS, ATTN_REGIMES, attn_inputs, attn_mask
+
+    def scores(qkv, bias, batch, L, H):
+        t = qkv.double().view(batch, L, 3, H, 64)
+        s = torch.einsum("bqhd,bkhd->bhqk", t[:, :, 0], t[:, :, 1]) * 0.125
+        return s if bias is None else s + bias.double()[:, None, None, :]
+
+    for L in (1, 2, 33, 129, 256, 385, 1024):
+        for regime in ATTN_REGIMES:
+            for mask in ATTN_MASKS:
+                qkv, bias = attn_inputs(2, L, 2, regime, mask, seed=L)
+                for dt in (torch.bfloat16, torch.float16):           # every operand is exact in both 16-bit formats
+                    assert torch.equal(qkv.to(dt).float(), qkv), (L, regime, mask, dt)
+                assert (bias is None) == (mask == "none")
+    batch, H = 4, 3
+    # peaked: most rows put > 0.9 on their top key
+    qkv, _ = attn_inputs(batch, 256, H, "peaked", "none", seed=1)
+    assert float(scores(qkv, None, batch, 256, H).softmax(-1).amax(-1).median()) >= 0.9
+    # offset: every score lifted by 90..100 -- the row max >= 89 everywhere
+    qkv, _ = attn_inputs(batch, 385, H, "offset", "none", seed=2)
+    s = scores(qkv, None, batch, 385, H)
+    assert float(s.amax(-1).min()) >= 89 and float(s.max()) <= 101
+    # late_max / early_max: one valid key beats every other by >= 20 (natural log) for every (query, head); late_max's is in the last 64-key
+    # block and 32-key tile
+    for L in (129, 256, 289, 385, 1024):
+        for regime, mask in (("late_max", "none"), ("late_max", "fusion"), ("early_max", "fusion"), ("early_max", "none")):
+            qkv, bias = attn_inputs(batch, L, H, regime, mask, seed=L)
+            s = scores(qkv, bias, batch, L, H)
+            top2 = s.topk(2, -1)
+            assert float((top2.values[..., 0] - top2.values[..., 1]).min()) >= 20, (L, regime, mask)
+            am = top2.indices[..., 0]
+            if regime == "early_max":
+                assert (am == 0).all()
+            else:
+                assert (am >= (L - 1) // 64 * 64).all() and (am >= (L - 1) // 32 * 32).all(), (L, mask)
+    # masks: a different one per sequence; fusion = cat(text, ones(Lv)) with a fully masked tile / block between valid keys
+    for L, unit in ((129, 32), (197, 32), (385, 64), (1024, 64)):
+        m = attn_mask(4, L, "fusion")
+        lv = 197 if L > 197 else L // 2
+        assert (m[:, L - lv:] == 1).all() and (m[:, 0] == 1).all()
+        assert len({tuple(r.tolist()) for r in m}) == 4
+        full = [b for b in range(4) if any(m[b, i * unit:(i + 1) * unit].sum() == 0 for i in range(1, L // unit))]
+        assert full, (L, unit)
+    for kind in ("tail", "fusion"):
+        m = attn_mask(3, 300, kind)
+        assert len({tuple(r.tolist()) for r in m}) == 3 and (m.sum(-1) >= 1).all()
+    assert (attn_mask(2, 70, "single").sum(-1) == 1).all() and attn_mask(2, 70, "all").sum() == 0
+
+
+# (L, regime, mask) through the emulator: the key-blocked path's stress cases of test_hip_long_attention (at two heads)
+EMU_CASES = ([(L, r, m) for L in (289, 385, 1024) for r in ("peaked", "late_max", "offset") for m in ("fusion", "single")]
+             + [(320, "gauss", "fusion"), (1023, "early_max", "fusion"), (257, "late_max", "tail"), (319, "gauss", "all"), (319, "offset", "all"),
+                (384, "late_max", "none")])
+
+
+def test_online_softmax_emulator_catches_planted_faults():
+    """The fault-free fp32 emulator of the key-blocked online softmax passes the fp32 forward tolerance against fp64 on every stress case of
+    the long path; each planted fault fails at least one of them (so the stress cases can see that bug in the HIP kernel)."""
+    worst = {}
+    for L, regime, mask in EMU_CASES:
+        for fault in (None,) + ATTN_FAULTS:
+            r = _emulator_errors(2, L, 2, regime, mask, seed=L + 14, fault=fault)
+            worst[fault] = max(worst.get(fault, 0.0), r)
+            if fault is None:
+                assert r <= 1.0, (L, regime, mask, r)
+    for fault in ATTN_FAULTS:
+        assert worst[fault] > 1.0, "planted fault %s passes every stress case" % fault
