@@ -121,13 +121,18 @@ __global__ __launch_bounds__(256) void attn_cls_kernel(const T* __restrict__ qkv
 // 6 workgroups x 96 K-steps = 190 us on an otherwise idle chip); here a workgroup owns 64 rows x 16 columns, its four waves split K four
 // ways and meet in LDS (fixed summation order: bit-reproducible), so the same problem is 48 workgroups x 12 steps (~10 us).
 // Optional fused LayerNorm of the A rows (K == the row width: statistics of the 64 rows recomputed per workgroup, two-pass in registers).
+// ABI 22 (the QA answer MLP, alpro_models.py:639-643): any N -- the last 16-column tile is masked (W rows clamped to N - 1 for the loads,
+// stores and epilogue reads stop at column N - 1, scalar stores where a float4 would cross N or ldc is not a multiple of 4) --, ReLU, and
+// RELU_MASK (the ReLU's backward: C = acc * [gate > 0], gate = the saved fp32 forward output).  Full tiles run the same instructions in the
+// same order as before: the existing heads' results are unchanged bit for bit.
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 
 template <int ACT, bool LN, int NW>
 __global__ __launch_bounds__(NW * 64) void gemm_rows_f32_kernel(const float* __restrict__ A, int64_t lda, const float* __restrict__ W, int64_t ldw,
                                                                 float* __restrict__ C, int64_t ldc, int M, int N, int K, const float* __restrict__ bias,
                                                                 const float* __restrict__ row_scale, const float* __restrict__ residual, int64_t ldr,
-                                                                const float* __restrict__ gamma, const float* __restrict__ beta, float eps) {
+                                                                const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
+                                                                const float* __restrict__ gate, int64_t ldg) {
   extern __shared__ __attribute__((aligned(16))) float smem_f[];
   float (*part)[64][16] = (float (*)[64][16])smem_f;          // [NW][64][16] partial sums of the K slices
   float (*stat)[2] = (float (*)[2])(smem_f + NW * 64 * 16);   // [64][2] mean, rstd of the tile's rows (fused LayerNorm)
@@ -192,7 +197,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_rows_f32_kernel(const float* __r
   const float* ap[4];
 #pragma unroll
   for (int f = 0; f < 4; ++f) ap[f] = A + (int64_t)min(m0 + f * 16 + r15, M - 1) * lda + k0 + kg * 4;
-  const float* wp = W + (int64_t)(n0 + r15) * ldw + k0 + kg * 4;
+  const float* wp = W + (int64_t)min(n0 + r15, N - 1) * ldw + k0 + kg * 4;   // columns past a ragged N (last tile) re-read row N - 1; never stored
   const float* gp = LN ? gamma + k0 + kg * 4 : nullptr;
   const float* bp = LN ? beta + k0 + kg * 4 : nullptr;
   f32x4v acc[4];
@@ -232,7 +237,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_rows_f32_kernel(const float* __r
   if (tid < 256) {
     const int row = tid >> 2, c4 = (tid & 3) * 4;
     const int m = m0 + row, n = n0 + c4;
-    if (m < M) {
+    if (m < M && n < N) {
       float v[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int w = 0; w < NW; ++w)   // fixed order: bit-reproducible
@@ -241,13 +246,23 @@ __global__ __launch_bounds__(NW * 64) void gemm_rows_f32_kernel(const float* __r
       const float sc = row_scale ? row_scale[m] : 1.0f;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
+        if (n + e >= N) continue;   // ragged last tile (ABI 22): nothing is read or written past column N - 1
         float x = v[e] + (bias ? bias[n + e] : 0.f);
         if (ACT == ALPRO_ACT_GELU) x = gelu_erf(x);
+        if (ACT == ALPRO_ACT_RELU) x = x < 0.f ? 0.f : x;                                   // NaN passes, as torch.relu
+        if (ACT == ALPRO_ACT_RELU_MASK) x = gate[(int64_t)m * ldg + n + e] > 0.f ? x : 0.f;   // ReLU backward: [H > 0] of the saved output
         x *= sc;
         if (residual) x += residual[(int64_t)m * ldr + n + e];
         v[e] = x;
       }
-      *(float4*)(C + (int64_t)m * ldc + n) = make_float4(v[0], v[1], v[2], v[3]);
+      float* c = C + (int64_t)m * ldc + n;
+      if (n + 4 <= N && (ldc & 3) == 0) {
+        *(float4*)c = make_float4(v[0], v[1], v[2], v[3]);
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          if (n + e < N) c[e] = v[e];
+      }
     }
   }
 }
@@ -256,22 +271,45 @@ __global__ __launch_bounds__(NW * 64) void gemm_rows_f32_kernel(const float* __r
 struct RowsArgs {
   const float* A; int64_t lda; const float* W; int64_t ldw; float* C; int64_t ldc; int M, N, K;
   const float* bias; const float* row_scale; const float* residual; int64_t ldr; const float* gamma; const float* beta; float eps;
+  const float* gate; int64_t ldg;
 };
 template <int ACT, bool LN, int NW>
 void launch_rows_inst(const RowsArgs& a, hipStream_t st) {
   constexpr int LDS = (NW * 64 * 16 + 128) * (int)sizeof(float);
   static DeviceOnce once;
   once.run([&] { (void)hipFuncSetAttribute((const void*)gemm_rows_f32_kernel<ACT, LN, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS); });
-  hipLaunchKernelGGL((gemm_rows_f32_kernel<ACT, LN, NW>), dim3(a.N / 16, (a.M + 63) / 64), dim3(NW * 64), LDS, st, a.A, a.lda, a.W, a.ldw, a.C, a.ldc, a.M,
-                     a.N, a.K, a.bias, a.row_scale, a.residual, a.ldr, a.gamma, a.beta, a.eps);
+  hipLaunchKernelGGL((gemm_rows_f32_kernel<ACT, LN, NW>), dim3((a.N + 15) / 16, (a.M + 63) / 64), dim3(NW * 64), LDS, st, a.A, a.lda, a.W, a.ldw, a.C, a.ldc, a.M,
+                     a.N, a.K, a.bias, a.row_scale, a.residual, a.ldr, a.gamma, a.beta, a.eps, a.gate, a.ldg);
 }
 template <int NW>
-void launch_rows_nw(const RowsArgs& a, bool ln, bool gelu, hipStream_t st) {
+void launch_rows_nw(const RowsArgs& a, bool ln, int act, hipStream_t st) {
+  if (act == ALPRO_ACT_RELU_MASK) { launch_rows_inst<ALPRO_ACT_RELU_MASK, false, NW>(a, st); return; }   // (no fused LayerNorm: refused by the entry point)
   if (ln) {
-    if (gelu) launch_rows_inst<ALPRO_ACT_GELU, true, NW>(a, st); else launch_rows_inst<ALPRO_ACT_NONE, true, NW>(a, st);
+    if (act == ALPRO_ACT_GELU) launch_rows_inst<ALPRO_ACT_GELU, true, NW>(a, st);
+    else if (act == ALPRO_ACT_RELU) launch_rows_inst<ALPRO_ACT_RELU, true, NW>(a, st);
+    else launch_rows_inst<ALPRO_ACT_NONE, true, NW>(a, st);
   } else {
-    if (gelu) launch_rows_inst<ALPRO_ACT_GELU, false, NW>(a, st); else launch_rows_inst<ALPRO_ACT_NONE, false, NW>(a, st);
+    if (act == ALPRO_ACT_GELU) launch_rows_inst<ALPRO_ACT_GELU, false, NW>(a, st);
+    else if (act == ALPRO_ACT_RELU) launch_rows_inst<ALPRO_ACT_RELU, false, NW>(a, st);
+    else launch_rows_inst<ALPRO_ACT_NONE, false, NW>(a, st);
   }
+}
+
+// checks shared by both entry points; K split over the waves of a workgroup: 16 waves for the long contractions (K = 3072: 12 steps per wave),
+// 8 below (K = 768: 6 steps)
+int launch_rows(const RowsArgs& a, int act, void* stream, const char* what) {
+  ALPRO_CHECK(a.A && a.W && a.C && a.M > 0 && a.N > 0 && a.K > 0, "%s: bad args", what);
+  ALPRO_CHECK(a.K % 64 == 0, "%s: K=%d must be a multiple of 64", what, a.K);
+  ALPRO_CHECK(a.lda % 4 == 0 && a.ldw % 4 == 0 && a.lda >= a.K && a.ldw >= a.K && a.ldc >= a.N && ((uintptr_t)a.A % 16) == 0 && ((uintptr_t)a.W % 16) == 0 &&
+              ((uintptr_t)a.C % 16) == 0, "%s: A / W rows must be 16-byte aligned and C 16-byte aligned with ldc >= N", what);
+  ALPRO_CHECK(!a.residual || a.ldr >= a.N, "%s: ldr < N", what);
+  const int nw = (a.K >= 2048 && a.K % 256 == 0) ? 16 : (a.K % 128 == 0 ? 8 : 4);
+  hipStream_t st = (hipStream_t)stream;
+  const bool ln = a.gamma != nullptr;
+  if (nw == 16) launch_rows_nw<16>(a, ln, act, st);
+  else if (nw == 8) launch_rows_nw<8>(a, ln, act, st);
+  else launch_rows_nw<4>(a, ln, act, st);
+  return check_launch(what);
 }
 
 }  // namespace
@@ -298,20 +336,15 @@ extern "C" int alpro_attn_cls_fwd(const void* qkv, int dtype, const float* qkv_c
 extern "C" int alpro_gemm_rows_f32(const float* A, int64_t lda, const float* W, int64_t ldw, float* C, int64_t ldc, int M, int N, int K,
                                    const float* bias, int act, const float* row_scale, const float* residual, int64_t ldr,
                                    const float* ln_gamma, const float* ln_beta, float ln_eps, void* stream) {
-  ALPRO_CHECK(A && W && C && M > 0 && N > 0 && K > 0, "alpro_gemm_rows_f32: bad args");
-  ALPRO_CHECK(N % 16 == 0 && K % 64 == 0, "alpro_gemm_rows_f32: N=%d must be a multiple of 16 and K=%d of 64", N, K);
-  ALPRO_CHECK(lda % 4 == 0 && ldw % 4 == 0 && ldc % 4 == 0 && ((uintptr_t)A % 16) == 0 && ((uintptr_t)W % 16) == 0 && ((uintptr_t)C % 16) == 0,
-              "alpro_gemm_rows_f32: rows must be 16-byte aligned");
-  ALPRO_CHECK(act == ALPRO_ACT_NONE || act == ALPRO_ACT_GELU, "alpro_gemm_rows_f32: act %d unsupported (none / gelu)", act);
+  ALPRO_CHECK(act == ALPRO_ACT_NONE || act == ALPRO_ACT_GELU || act == ALPRO_ACT_RELU, "alpro_gemm_rows_f32: act %d unsupported (none / gelu / relu)", act);
   ALPRO_CHECK(!ln_gamma == !ln_beta, "alpro_gemm_rows_f32: LayerNorm needs both gamma and beta");
-  ALPRO_CHECK(!ln_gamma || K % 64 == 0, "alpro_gemm_rows_f32: fused LayerNorm needs K a multiple of 64 (got %d)", K);
-  // K split over the waves of a workgroup: 16 waves for the long contractions (K = 3072: 12 steps per wave), 8 below (K = 768: 6 steps)
-  const int nw = (K >= 2048 && K % 256 == 0) ? 16 : (K % 128 == 0 ? 8 : 4);
-  const RowsArgs ra{A, lda, W, ldw, C, ldc, M, N, K, bias, row_scale, residual, ldr, ln_gamma, ln_beta, ln_eps};
-  hipStream_t st = (hipStream_t)stream;
-  const bool ln = ln_gamma != nullptr, ge = act == ALPRO_ACT_GELU;
-  if (nw == 16) launch_rows_nw<16>(ra, ln, ge, st);
-  else if (nw == 8) launch_rows_nw<8>(ra, ln, ge, st);
-  else launch_rows_nw<4>(ra, ln, ge, st);
-  return check_launch("alpro_gemm_rows_f32");
+  const RowsArgs ra{A, lda, W, ldw, C, ldc, M, N, K, bias, row_scale, residual, ldr, ln_gamma, ln_beta, ln_eps, nullptr, 0};
+  return launch_rows(ra, act, stream, "alpro_gemm_rows_f32");
+}
+
+extern "C" int alpro_gemm_rows_f32_relu_mask(const float* A, int64_t lda, const float* W, int64_t ldw, float* C, int64_t ldc, int M, int N, int K,
+                                             const float* gate, int64_t ldg, void* stream) {
+  ALPRO_CHECK(gate && ldg >= N, "alpro_gemm_rows_f32_relu_mask: the saved ReLU output (M, ldg >= N) is required");
+  const RowsArgs ra{A, lda, W, ldw, C, ldc, M, N, K, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0.f, gate, ldg};
+  return launch_rows(ra, ALPRO_ACT_RELU_MASK, stream, "alpro_gemm_rows_f32_relu_mask");
 }

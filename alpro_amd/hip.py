@@ -12,7 +12,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ALPRO_HIP_LIB") or os.path.join(_HERE, "lib", "libalpro_hip.so")  # ALPRO_HIP_LIB: tools/ load the ablation build
 
 F32, BF16, F16 = 0, 1, 2
-ACT_NONE, ACT_GELU, ACT_RELU, ACT_GELU_BWD, ACT_GELU_SAVE_GRAD, ACT_MUL_SAVED = 0, 1, 2, 3, 4, 5
+ACT_NONE, ACT_GELU, ACT_RELU, ACT_GELU_BWD, ACT_GELU_SAVE_GRAD, ACT_MUL_SAVED, ACT_RELU_MASK = 0, 1, 2, 3, 4, 5, 6
+POOL_MODES = {"mean": 0, "max": 1, "lse": 2}   # alpro_clip_pool (run_video_qa.py score_agg_func)
 MAP_IDENTITY, MAP_SKIP_CLS, MAP_FRAME_TOKENS, MAP_PATCH_EMBED = 0, 1, 2, 3
 ADD_IDENTITY, ADD_PRE_SPATIAL, ADD_PRE_MLP, ADD_PRE_TEMPORAL = 0, 1, 2, 3
 EMIT_NONE, EMIT_ROWS, EMIT_FRAME, EMIT_SKIP_CLS = 0, 1, 2, 3
@@ -24,7 +25,8 @@ EXPORTS = ["alpro_hip_last_error", "alpro_hip_abi_version", "alpro_hip_set_optio
            "alpro_attn_temporal_fwd", "alpro_attn_fwd", "alpro_patchify", "alpro_cls_mean_residual",
            "alpro_vit_final_pool", "alpro_bert_embed_fwd", "alpro_cast_from_f32", "alpro_attn_bwd", "alpro_attn_temporal_bwd",
            "alpro_layernorm_bwd", "alpro_transpose", "alpro_transpose_batch", "alpro_gelu_bwd", "alpro_cls_mean_bwd", "alpro_scatter_add_rows", "alpro_gather_cast", "alpro_sumsq", "alpro_adamw_step", "alpro_gemm_tn_acc", "alpro_gemm_tn_acc_ws", "alpro_gemm_tn_workspace_bytes", "alpro_gemm_tn_ranges", "alpro_colsum_acc", "alpro_softmax_xent", "alpro_vtc_loss_fwd", "alpro_vtc_loss_bwd", "alpro_prepare_clips", "alpro_loss_scale_update", "alpro_add_layernorm_fwd", "alpro_layernorm_bwd_emit", "alpro_gemm_batch", "alpro_tproj_small", "alpro_attn_cls_fwd", "alpro_gemm_rows_f32", "alpro_gather_seq_fwd", "alpro_gather_seq_bwd", "alpro_scatter_add_rows_ordered",
-           "alpro_hip_sched_workspace_bytes", "alpro_hip_set_sched_workspace", "alpro_hip_release_stream", "alpro_gemm_qkv_tattn", "alpro_add_layernorm_pre_mlp2", "alpro_adamw_step_lp"]
+           "alpro_hip_sched_workspace_bytes", "alpro_hip_set_sched_workspace", "alpro_hip_release_stream", "alpro_gemm_qkv_tattn", "alpro_add_layernorm_pre_mlp2", "alpro_adamw_step_lp",
+           "alpro_gemm_rows_f32_relu_mask", "alpro_clip_pool"]
 
 
 class GemmDesc(ctypes.Structure):
@@ -52,7 +54,7 @@ class TransposeJob(ctypes.Structure):
                 ("R", ctypes.c_int32), ("C", ctypes.c_int32), ("Rpad", ctypes.c_int32), ("tile0", ctypes.c_int32)]   # 48 bytes
 
 
-ABI_VERSION = 21
+ABI_VERSION = 22
 _lib = None
 
 
@@ -107,6 +109,8 @@ def load():
     lib.alpro_attn_fwd.argtypes = [vp, vp, i32, i32, i32, i32, f32, vp, vp, f32, u32, vp, i32, vp, vp]
     lib.alpro_attn_cls_fwd.argtypes = [vp, i32, vp, vp, vp, i32, i32, i32, i32, f32, f32, u32, vp]
     lib.alpro_gemm_rows_f32.argtypes = [vp, i64, vp, i64, vp, i64, i32, i32, i32, vp, i32, vp, vp, i64, vp, vp, f32, vp]
+    lib.alpro_gemm_rows_f32_relu_mask.argtypes = [vp, i64, vp, i64, vp, i64, i32, i32, i32, vp, i64, vp]
+    lib.alpro_clip_pool.argtypes = [vp, i64, vp, i64, vp, i32, i32, i32, i32, vp]
     lib.alpro_gemm_c2_tiled_rows.argtypes = [i64, i64, i64, i32]
     lib.alpro_gemm_c2_tiled_rows.restype = i64
     lib.alpro_patchify.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
@@ -611,7 +615,8 @@ def attn_cls(qkv, qkv_cls, batch, L, H, scale, group=1, key_bias=None, drop_p=0.
 
 def gemm_rows(a, w, bias=None, act=ACT_NONE, row_scale=None, residual=None, ln=None, out=None):
     """fp32 Linear on a handful of rows (alpro_gemm_rows_f32): out = residual + row_scale * act(LN(a) @ w.T + bias); a (M, K), w (N, K) fp32
-    (row-strided views allowed), ln = (gamma, beta, eps) fuses the LayerNorm of a's rows."""
+    (row-strided views allowed), ln = (gamma, beta, eps) fuses the LayerNorm of a's rows.  act: ACT_NONE / ACT_GELU / ACT_RELU; K % 64 == 0,
+    any N (ABI 22: the last 16-column tile is masked).  `out` may be a row-strided view (e.g. the first N columns of a padded buffer)."""
     lib = load()
     _dev(a, torch.float32); _dev(w, torch.float32)
     M, K = a.shape
@@ -632,6 +637,41 @@ def gemm_rows(a, w, bias=None, act=ACT_NONE, row_scale=None, residual=None, ln=N
                                    _ptr(_dev(row_scale, torch.float32)) if row_scale is not None else None,
                                    _ptr(residual), residual.stride(0) if residual is not None else 0, _ptr(g), _ptr(b), eps, _stream()), "alpro_gemm_rows_f32")
     return out
+
+
+def gemm_rows_relu_mask(a, w, gate, out=None):
+    """Backward of a ReLU Linear on a handful of rows (alpro_gemm_rows_f32_relu_mask): out = (a @ w.T) * (gate > 0); a (M, K), w (N, K),
+    gate (M, N) = the saved fp32 ReLU output; K % 64 == 0, any N."""
+    lib = load()
+    _dev(a, torch.float32); _dev(w, torch.float32); _dev(gate, torch.float32)
+    M, K = a.shape
+    N = w.shape[0]
+    assert w.shape[1] == K and a.stride(1) == 1 and w.stride(1) == 1 and gate.shape == (M, N) and gate.stride(1) == 1
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.float32, device=a.device)
+    _dev(out, torch.float32)
+    _check(lib.alpro_gemm_rows_f32_relu_mask(_ptr(a), a.stride(0), _ptr(w), w.stride(0), _ptr(out), out.stride(0), M, N, K, _ptr(gate), gate.stride(0),
+                                             _stream()), "alpro_gemm_rows_f32_relu_mask")
+    return out
+
+
+def clip_pool(logits, C, mode="mean"):
+    """Multi-clip QA pooling (alpro_clip_pool): logits (B*C, A) fp32, rows question-major (b*C + c), row-strided views allowed ->
+    (pooled (B, A) fp32, pred (B,) int64 = argmax of each pooled row).  mode: 'mean' / 'max' / 'lse' (run_video_qa.py score_agg_func)."""
+    if mode not in POOL_MODES:
+        raise ValueError("clip_pool: mode %r, expect one of %s" % (mode, sorted(POOL_MODES)))
+    lib = load()
+    _dev(logits, torch.float32)
+    if logits.dim() != 2 or logits.stride(1) != 1:
+        raise RuntimeError("clip_pool: logits must be (B*C, A) with unit column stride")
+    if C < 1 or logits.shape[0] % C:
+        raise RuntimeError("clip_pool: %d rows are not a whole number of groups of C=%d clips" % (logits.shape[0], C))
+    B, A = logits.shape[0] // C, logits.shape[1]
+    pooled = torch.empty((B, A), dtype=torch.float32, device=logits.device)
+    pred = torch.empty((B,), dtype=torch.int64, device=logits.device)
+    _check(lib.alpro_clip_pool(_ptr(logits), logits.stride(0), _ptr(pooled), pooled.stride(0), _ptr(pred), B, C, A, POOL_MODES[mode], _stream()),
+           "alpro_clip_pool")
+    return pooled, pred
 
 
 def patchify(img, dtype):

@@ -536,15 +536,90 @@ class AlproForVideoTextRetrieval(AlproBaseModel):
         return dict(logits=_linear32(out[:, 0, :], self.itm_head), itc_scores=video_feat @ text_feat.t() / self.temp)
 
 
+_HEAD_ROW_CHUNK = 512   # alpro_gemm_rows_f32 is sized for a handful of rows (_rows_ok): multi-clip evaluation's B * C rows run in chunks of this many
+
+
+class _QAHead(torch.autograd.Function):
+    """The VideoQA answer MLP and its loss (alpro_models.py:639-643,680-683) as one node, fp32 throughout:
+        H = relu(X W1^T + b1)   alpro_gemm_rows_f32, act = ReLU
+        Z = H W2^T + b2         alpro_gemm_rows_f32, any num_labels (the last 16-column tile is masked)
+        loss_rows = CE(Z, y)    alpro_softmax_xent, which also writes softmax(Z) - onehot(y) for the backward
+    Backward: dZ = (softmax - onehot) * d(loss_rows) [+ d(logits)], dH = (dZ W2) * [H > 0] (alpro_gemm_rows_f32_relu_mask on the saved H),
+    dX = dH W1, weight gradients as the small NT products of _Linear32.  Z lives in a (M, A rounded up to 64) buffer: `logits` is its
+    first A columns (rows 8-byte aligned for softmax_xent at any A; the zero-padded gradient feeds the next K-contraction directly)."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, labels):
+        M, A = x.shape[0], w2.shape[0]
+        Ap = (A + 63) // 64 * 64
+        w1_, w2_ = w1.detach().contiguous(), w2.detach().contiguous()
+        h = torch.empty((M, w1.shape[0]), dtype=torch.float32, device=x.device)
+        z = torch.empty((M, Ap), dtype=torch.float32, device=x.device)
+        logits = z[:, :A]
+        for r in range(0, M, _HEAD_ROW_CHUNK):
+            s = slice(r, min(M, r + _HEAD_ROW_CHUNK))
+            hip.gemm_rows(x[s], w1_, bias=b1.detach(), act=hip.ACT_RELU, out=h[s])
+            hip.gemm_rows(h[s], w2_, bias=b2.detach(), out=logits[s])
+        dl = None
+        if labels is None:
+            loss_rows = torch.zeros(M, dtype=torch.float32, device=x.device)
+            ctx.mark_non_differentiable(loss_rows)
+        elif any(ctx.needs_input_grad[:5]):
+            one = torch.ones(1, dtype=torch.float32, device=x.device)
+            loss_rows, dl = hip.softmax_xent(logits, labels, grad_dtype=torch.float32, grad_scale=one)   # dl: (M, Ap), zero past column A
+        else:
+            loss_rows = hip.softmax_xent(logits, labels)
+        ctx.save_for_backward(x, w1, w2, h, dl)
+        ctx.set_materialize_grads(False)
+        return logits, loss_rows
+
+    @staticmethod
+    def backward(ctx, dlogits, dloss_rows):
+        x, w1, w2, h, dl = ctx.saved_tensors
+        M, A = x.shape[0], w2.shape[0]
+        Ap = (A + 63) // 64 * 64
+        if dl is not None and dloss_rows is not None:
+            g = dl * dloss_rows.reshape(M, 1)
+        else:
+            g = torch.zeros((M, Ap), dtype=torch.float32, device=x.device)
+        if dlogits is not None:
+            g[:, :A] += dlogits
+        w2t = _pad_k(w2.detach().t().contiguous(), 64)                     # (hidden, Ap): the contraction over the labels, zero-padded like g
+        dh = torch.empty_like(h)
+        for r in range(0, M, _HEAD_ROW_CHUNK):
+            s = slice(r, min(M, r + _HEAD_ROW_CHUNK))
+            hip.gemm_rows_relu_mask(g[s], w2t, h[s], out=dh[s])
+        dx = None
+        if ctx.needs_input_grad[0]:
+            w1t = w1.detach().t().contiguous()
+            dx = torch.empty_like(x)
+            for r in range(0, M, _HEAD_ROW_CHUNK):
+                s = slice(r, min(M, r + _HEAD_ROW_CHUNK))
+                hip.gemm_rows(dh[s], w1t, out=dx[s])
+        gz = g[:, :A]
+        dw2 = hip.gemm(_pad_k(gz.t().contiguous()), _pad_k(h.t().contiguous()), out_dtype=torch.float32) if ctx.needs_input_grad[3] else None
+        db2 = gz.sum(0) if ctx.needs_input_grad[4] else None
+        dw1 = hip.gemm(_pad_k(dh.t().contiguous()), _pad_k(x.t().contiguous()), out_dtype=torch.float32) if ctx.needs_input_grad[1] else None
+        db1 = dh.sum(0) if ctx.needs_input_grad[2] else None
+        return dx, dw1, db1, dw2, db2, None
+
+
 class AlproForSequenceClassification(AlproBaseModel):
-    """VideoQA head (alpro_models.py:633-724): same encoders + an MLP classifier.  Kept for API completeness;
-    the QA task itself is outside the graded hot path (SURVEY.md section 2 #1)."""
+    """VideoQA model (alpro_models.py:633-724, driven by run_video_qa.py): the encoders + an MLP classifier over the fusion [CLS] row.
+    Same constructor, forward(batch) -> dict(loss, logits) and state_dict keys as the reference; results differ by fp32 rounding order only.
+      * the fusion input is a row gather of the text and video sequences (alpro_gather_seq_*), not a torch.cat;
+      * the last fusion layer's row-wise tail runs on the B [CLS] rows only -- the classifier reads nothing else (ALPRO_FUSION_TAIL_ROWS=0:
+        every row, for A/B);
+      * the answer MLP and its cross-entropy are one fp32 node on the row kernel (_QAHead).
+    encode_questions / encode_clips / answer_logits split forward at its seams so that multi-clip evaluation (alpro_amd/qa_eval.py) encodes
+    each question once and each clip once."""
 
     def __init__(self, config, video_enc_cfg, input_format='RGB'):
         super().__init__(config, video_enc_cfg=video_enc_cfg)
         self.text_encoder = BertModel.from_pretrained('bert-base-uncased', config=self.bert_config, add_pooling_layer=False)
         self.classifier = nn.Sequential(nn.Linear(config.hidden_size, config.hidden_size * 2), nn.ReLU(True),
                                         nn.Linear(config.hidden_size * 2, config.num_labels))
+        self.fusion_tail_rows = os.environ.get("ALPRO_FUSION_TAIL_ROWS", "1") != "0"
 
     def _text_embeds(self, input_ids, attention_mask):
         return self.text_encoder(input_ids, attention_mask=attention_mask, return_dict=True, mode='text').last_hidden_state
@@ -552,18 +627,44 @@ class AlproForSequenceClassification(AlproBaseModel):
     def _fusion(self, embeds, attention_mask):
         return self.text_encoder(encoder_embeds=embeds, attention_mask=attention_mask, return_dict=True, mode='fusion').last_hidden_state
 
-    def _logits(self, batch):
+    def encode_questions(self, text_input_ids, text_input_mask):
+        """(n, Lt) -> text encoder output (n, Lt, D) fp32."""
+        return self._text_embeds(text_input_ids, text_input_mask)
+
+    def encode_clips(self, visual_inputs):
+        """(n, T, C, H, W) clips -> visual encoder output (n, 1 + N, D) fp32."""
+        return self._forward_visual_embeds(visual_inputs)
+
+    def answer_logits(self, text_embeds, text_input_mask, video_embeds, ti, vi, labels=None):
+        """Fusion + answer MLP over S (question, clip) pairs: sequence s = [text_embeds[ti[s]] ; video_embeds[vi[s]]] (ti, vi (S,) int64 on
+        the device; the rows are gathered, never repeated) -> (logits (S, num_labels) fp32, per-pair cross-entropy (S,); zeros if labels is None)."""
+        S, Lt = ti.numel(), text_embeds.shape[1]
+        L = Lt + video_embeds.shape[1]
+        att = torch.ones((S, L), dtype=text_input_mask.dtype, device=text_input_mask.device)
+        att[:, :Lt] = text_input_mask[ti]
+        bert = self.text_encoder
+        tail = self.fusion_tail_rows and text_embeds.is_cuda and getattr(bert.encoder.layer[-1], 'fuse_residual_ln', False)
+        rows = torch.arange(S, device=ti.device, dtype=torch.long) * L if tail else None
+        out = bert(encoder_embeds_parts=(text_embeds, video_embeds, ti, vi), attention_mask=att, return_dict=True, mode='fusion',
+                   out_rows=rows).last_hidden_state
+        cls_rows = (out if rows is not None else out[:, 0, :]).contiguous().float()
+        if labels is not None:
+            labels = labels.contiguous()
+        return _QAHead.apply(cls_rows, self.classifier[0].weight, self.classifier[0].bias, self.classifier[2].weight, self.classifier[2].bias, labels)
+
+    def _logits(self, batch, labels=None):
         visual_inputs, mask = batch['visual_inputs'], batch['text_input_mask']
-        text_embeds = self._text_embeds(batch['text_input_ids'], mask)
-        image_embeds = self._forward_visual_embeds(visual_inputs)
-        image_atts = torch.ones(image_embeds.size()[:-1], dtype=torch.long, device=visual_inputs.device)
-        out = self._fusion(torch.cat([text_embeds, image_embeds], dim=1), torch.cat([mask, image_atts], dim=1))
-        return _linear32(F.relu(_linear32(out[:, 0, :], self.classifier[0])), self.classifier[2])
+        text_embeds = self.encode_questions(batch['text_input_ids'], mask)
+        video_embeds = self.encode_clips(visual_inputs)
+        idx = torch.arange(visual_inputs.shape[0], device=visual_inputs.device)
+        return self.answer_logits(text_embeds, mask, video_embeds, idx, idx, labels)
 
     def forward(self, batch):
-        prediction = self._logits(batch)
         targets = batch['labels']
-        return dict(loss=F.cross_entropy(prediction, targets) if targets is not None else 0, logits=prediction)
+        prediction, loss_rows = self._logits(batch, targets)
+        return dict(loss=loss_rows.mean() if targets is not None else 0, logits=prediction)
 
     def forward_inference(self, batch):
-        return self._logits(batch)
+        """-> logits, equal to forward(batch)['logits'].  The reference's version (alpro_models.py:686-724) calls self.text_encoder.bert on
+        a BertModel and raises AttributeError; this is the computation it evidently intends."""
+        return self._logits(batch)[0]

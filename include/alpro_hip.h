@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define ALPRO_HIP_ABI_VERSION 21
+#define ALPRO_HIP_ABI_VERSION 22
 
 enum { ALPRO_OK = 0, ALPRO_ERR_INVALID = 1, ALPRO_ERR_LAUNCH = 2 };
 enum { ALPRO_F32 = 0, ALPRO_BF16 = 1, ALPRO_F16 = 2 };
@@ -39,7 +39,10 @@ enum { ALPRO_ACT_NONE = 0, ALPRO_ACT_GELU = 1, ALPRO_ACT_RELU = 2, ALPRO_ACT_GEL
        /* round 3: the GELU Linear's forward writes gelu'(pre-activation) into C2 instead of the pre-activation (GELU_SAVE_GRAD, C2 required),
         * and its dgrad multiplies by the saved value (MUL_SAVED: C = (alpha*acc + bias) * C2[m, n], C2 read only) -- the ~13 VALU operations
         * per element of recomputing gelu' in the backward epilogue (the slowest dgrad of the model in round 2) become one multiply. */
-       ALPRO_ACT_GELU_SAVE_GRAD = 4, ALPRO_ACT_MUL_SAVED = 5 };
+       ALPRO_ACT_GELU_SAVE_GRAD = 4, ALPRO_ACT_MUL_SAVED = 5,
+       /* ABI 22, alpro_gemm_rows_f32_relu_mask only: the backward of a ReLU Linear, C = acc * [gate[m, n] > 0] with gate = the saved fp32
+        * ReLU output (the QA answer MLP, alpro_models.py:639-643) */
+       ALPRO_ACT_RELU_MASK = 6 };
 
 /* Row maps: how GEMM/LayerNorm row m addresses the (B, 1 + N*T, D) token tensor whose patch token
  * (n, t) lives at row 1 + n*T + t of its clip (vit.py:147 'b (h w t) m').
@@ -218,11 +221,28 @@ int alpro_attn_cls_fwd(const void* qkv, int dtype, const float* qkv_cls, const f
 /* The Linears (and pre-LayerNorms) of the precise CLS-row side path: C[M, N] = residual + row_scale[m] * act(LN(A)[M, K] W[N, K]^T + bias), all
  * fp32 (exact fp32 MFMA, fixed summation order), for M = B or B*T rows against a full (N, K) fp32 master weight (vit.py:84,98,59-65 / xbert.py
  * :304-316,357,421,435 applied to the CLS rows only).  ln_gamma / ln_beta (K,) or NULL: LayerNorm of the A rows over their K elements fused
- * into the operand load (vit.py:180 norm1, :200 norm2).  act: ALPRO_ACT_NONE / ALPRO_ACT_GELU (exact erf).  N % 16 == 0, K % 64 == 0. */
+ * into the operand load (vit.py:180 norm1, :200 norm2).  act: ALPRO_ACT_NONE / ALPRO_ACT_GELU (exact erf) / ALPRO_ACT_RELU (ABI 22).
+ * K % 64 == 0; A and W rows 16-byte aligned (lda, ldw multiples of 4), C 16-byte aligned, ldc >= N.  Any N >= 1 (ABI 22; before: N % 16 == 0):
+ * the last 16-column tile is masked, so nothing at or past column N of C, bias or residual is touched (the QA answer layer's 1500 / 3129
+ * labels).  Columns of full tiles with ldc % 4 == 0 are computed and stored exactly as before ABI 22. */
 int alpro_gemm_rows_f32(const float* A, int64_t lda, const float* W, int64_t ldw, float* C, int64_t ldc, int M, int N, int K,
                         const float* bias /* (N) or NULL */, int act, const float* row_scale /* (M) or NULL */,
                         const float* residual /* (M, ldr) or NULL */, int64_t ldr, const float* ln_gamma, const float* ln_beta, float ln_eps,
                         void* stream);
+
+/* ABI 22: the backward of a ReLU Linear on a handful of rows (the QA answer MLP: dH = (dZ W2) * [H > 0]): C[M, N] = (A[M, K] W[N, K]^T) *
+ * [gate[m, n] > 0], gate = the fp32 ReLU output the forward saved ((M, ldg >= N), read only; an exact 0 masks, as torch's threshold_backward).
+ * Same kernel, shape rules and summation order as alpro_gemm_rows_f32 with act = ALPRO_ACT_RELU_MASK; no bias, LayerNorm, row scale or
+ * residual. */
+int alpro_gemm_rows_f32_relu_mask(const float* A, int64_t lda, const float* W, int64_t ldw, float* C, int64_t ldc, int M, int N, int K,
+                                  const float* gate, int64_t ldg, void* stream);
+
+/* ABI 22: multi-clip pooling of QA logits (run_video_qa.py:249-276 score_agg_func): logits (B*C, A) fp32 with row stride ld, rows
+ * question-major (row b*C + c = clip c of question b) -> pooled (B, A) fp32 (row stride ldo) and pred (B,) int64 = the first index of the
+ * pooled row's maximum.  mode 0 = mean (sum over c in order, / C), 1 = max, 2 = lse (m + log(sum_c exp(x_c - m)), m = max over c; -inf
+ * when every clip is -inf, as torch.logsumexp).  One workgroup per question, no atomics: bitwise reproducible.  C >= 1, A >= 1. */
+enum { ALPRO_POOL_MEAN = 0, ALPRO_POOL_MAX = 1, ALPRO_POOL_LSE = 2 };
+int alpro_clip_pool(const float* logits, int64_t ld, float* pooled, int64_t ldo, int64_t* pred, int B, int C, int A, int mode, void* stream);
 
 /* Full (bidirectional) attention over `batch` sequences of 1 <= L <= ALPRO_ATTN_MAX_L tokens, head_dim 64:
  * spatial half of divided attention (vit.py:180 on (B*T, 1+N) tokens, :81-96) and the BERT
