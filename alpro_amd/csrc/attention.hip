@@ -968,9 +968,10 @@ extern "C" int alpro_attn_fwd(const void* qkv, void* out, int dtype, int batch, 
 
 extern "C" int alpro_attn_temporal_fwd(const void* qkv, void* out, int dtype, int64_t rows, int T, int H, float scale, float* lse, void* stream) {
   ALPRO_CHECK(qkv && out && rows > 0 && H > 0, "alpro_attn_temporal_fwd: bad args");
-  ALPRO_CHECK(T > 0 && 32 % T == 0, "alpro_attn_temporal_fwd: num_frm=%d must divide 32", T);
+  ALPRO_CHECK(T > 0 && T <= ALPRO_ATTN_MAX_T, "alpro_attn_temporal_fwd: num_frm=%d unsupported (1..%d = ALPRO_ATTN_MAX_T)", T, ALPRO_ATTN_MAX_T);
   ALPRO_CHECK(rows % T == 0, "alpro_attn_temporal_fwd: rows=%lld not a multiple of T=%d", (long long)rows, T);
   ALPRO_CHECK(((uintptr_t)qkv % 16) == 0 && ((uintptr_t)out % 16) == 0, "alpro_attn_temporal_fwd: pointers must be 16-byte aligned");
+  if (32 % T != 0) return attn_temporal_any_fwd(qkv, out, dtype, rows, T, H, scale, lse, (hipStream_t)stream);
   const int64_t units = ((rows + 31) / 32) * H;
   int64_t grid = (units + 3) / 4;
   if (grid > 256 * 8) grid = 256 * 8;

@@ -1509,7 +1509,9 @@ extern "C" int alpro_attn_bwd(const void* qkv, const void* out, const void* dout
 extern "C" int alpro_attn_temporal_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int dtype,
                                        int64_t rows, int T, int H, float scale, void* stream) {
   ALPRO_CHECK(qkv && out && dout && lse && dqkv && rows > 0 && H > 0, "alpro_attn_temporal_bwd: bad args");
-  ALPRO_CHECK(T > 0 && 32 % T == 0 && rows % T == 0, "alpro_attn_temporal_bwd: num_frm=%d must divide 32 and rows", T);
+  ALPRO_CHECK(T > 0 && T <= ALPRO_ATTN_MAX_T, "alpro_attn_temporal_bwd: num_frm=%d unsupported (1..%d = ALPRO_ATTN_MAX_T)", T, ALPRO_ATTN_MAX_T);
+  ALPRO_CHECK(rows % T == 0, "alpro_attn_temporal_bwd: rows=%lld not a multiple of T=%d", (long long)rows, T);
+  if (32 % T != 0) return attn_temporal_any_bwd(qkv, out, dout, lse, dqkv, dtype, rows, T, H, scale, (hipStream_t)stream);
   const int64_t chunks = (rows + 31) / 32;
   if (dtype != ALPRO_F32) {
     const int64_t units = chunks * H;

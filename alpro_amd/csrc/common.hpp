@@ -264,6 +264,10 @@ int attn_long_fwd(const void* qkv, void* out, int dtype, int batch, int L, int H
                   uint32_t drop_seed, const float* cls_q, int cls_group, float* cls_out, hipStream_t st);
 int attn_long_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int dtype, int batch, int L, int H, float scale,
                   const float* key_bias, float drop_p, uint32_t drop_seed, hipStream_t st);
+// Temporal attention over a frame count that does not divide 32 (attention_temporal_any.hip): what alpro_attn_temporal_fwd / _bwd launch there.
+int attn_temporal_any_fwd(const void* qkv, void* out, int dtype, int64_t rows, int T, int H, float scale, float* lse, hipStream_t st);
+int attn_temporal_any_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int dtype, int64_t rows, int T, int H,
+                          float scale, hipStream_t st);
 
 // Tuning knobs (measurement aids, not part of the arithmetic): initialised ONCE from the environment when the library is
 // loaded (ALPRO_GEMM_TILE / ALPRO_GEMM_GRID / ALPRO_GEMM_TUNE / ALPRO_TN_SPLITS), changed at run time only through

@@ -205,7 +205,13 @@ int alpro_add_layernorm_pre_mlp2(const float* x_in, const void* delta_t, const f
 /* Divided space-time attention, temporal half (vit.py:146-157 -> Attention.forward :81-96):
  * rows = B*N*T tokens in (b, n, t) order, each group of T consecutive rows attends within itself.
  * qkv (rows, 3*H*64) as written by the qkv Linear, out (rows, H*64) == 'transpose(1,2).reshape'.
- * T must divide 32.  softmax(q k^T * scale) v on MFMA with a block-diagonal group mask. */
+ * 1 <= T <= ALPRO_ATTN_MAX_T, rows a multiple of T (need not be a multiple of 32), qkv / out 16-byte aligned.
+ * softmax(q k^T * scale) v on MFMA.  Dispatch is by T alone: T dividing 32 runs the block-diagonal kernels (one 32-row tile holds
+ * whole groups; attention.hip / attention_bwd.hip), every other T the windowed kernels of attention_temporal_any.hip (a 32-row unit
+ * streams the rows of every group it touches, online softmax); T > ALPRO_ATTN_MAX_T is refused.  Both paths write lse as
+ * ((rows + 31) / 32, H, 32): row c*32 + r of head h at [c, h, r].  alpro_attn_temporal_bwd follows the same rule, reads that lse,
+ * and uses no atomics and no workspace on either path. */
+#define ALPRO_ATTN_MAX_T 128
 int alpro_attn_temporal_fwd(const void* qkv, void* out, int dtype, int64_t rows, int T, int H, float scale,
                             float* lse /* optional (ceil(rows/32), H, 32) row log-sum-exp for the backward */, void* stream);
 
