@@ -12,23 +12,14 @@
 //                       tile with a block-diagonal mask, one wave per (32 tokens, head).
 // Storage dtype T: bf16/f16 (K=16 MFMA) or f32 (K=2 MFMA, exact mode); a 16-byte chunk is the unit.
 #include "common.hpp"
+#include "attn_tile.hpp"
 
 namespace alpro {
 namespace {
 
-constexpr int HD = 64;
-
-template <typename T> struct AttnCfg {
-  static constexpr int E = sizeof(T);
-  static constexpr int CN = 16 / E;        // elements per 16-byte chunk
-  static constexpr int RB = HD * E;        // bytes per head row
-  static constexpr int CPR = RB / 16;      // chunks per head row (8 or 16)
-  static constexpr int KS = CPR / 2;       // MFMA chunk-steps over head_dim (two lane halves per step)
-  static constexpr int CPT = 16 / CN;      // P chunks per 32-key tile (2 or 4)
-};
-
+// The K and V images of these kernels are layouts of their own (k_swz, v_swz below), not the U tile of attn_tile.hpp.
 template <typename T> __device__ __forceinline__ int k_swz(int row, int chunk) {
-  if (AttnCfg<T>::CPR == 8) return chunk ^ ((row >> 1) & 7);  // 128-B rows: two rows per 256-B bank row
+  if (TileCfg<T>::CPR == 8) return chunk ^ ((row >> 1) & 7);  // 128-B rows: two rows per 256-B bank row
   return chunk ^ (row & 15);                                   // 256-B rows
 }
 
@@ -37,7 +28,7 @@ template <typename T> struct Col4;
 template <> struct Col4<float> {
   typedef u32x4 type;
   static __device__ __forceinline__ u32x4 load(const char* v, int key0, int d) {
-    const float* p = (const float*)(v + key0 * AttnCfg<float>::RB) + d;
+    const float* p = (const float*)(v + key0 * TileCfg<float>::RB) + d;
     return mk4(f2u(p[0]), f2u(p[64]), f2u(p[128]), f2u(p[192]));
   }
 };
@@ -65,39 +56,22 @@ template <typename T> __device__ __forceinline__ u32x4 load_vt_chunk(const char*
 template <> __device__ __forceinline__ u32x4 load_vt_chunk<float>(const char* vt, int cc, int lane, int dt) {
   return Col4<float>::load(vt, 8 * cc + 4 * (lane >> 5), dt * 32 + (lane & 31));  // one quad per chunk: regs 4cc..4cc+3
 }
-// 16-bit: hardware transpose read.  ds_read_b64_tr_b16 semantics (probed on gfx950, tools/probe_tr.hip):
-// within each 16-lane group, lane l receives element (l & 3) of the 8-byte piece addressed by lane
-// (l >> 2) + 4j, j = 0..3.  Lane p therefore points at key row key0 + (p >> 2), d-quad (p & 3) of its
-// group's 16-wide d block, and every lane gets 4 consecutive keys of its own d column.
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ u32x2 tr_quad(const char* vt, int key0, int lane, int dt) {
+// 16-bit: hardware transpose read (lane map: attn_tile.hpp) of the V image: lane p of a 16-lane group points at key row key0 + (p >> 2),
+// d-quad (p & 3) of its group's 16-wide d block -- the 32-byte pair of chunks `seg`, swizzled as v_swz does.
+__device__ __forceinline__ u32x2 tr_quad_v(const char* vt, int key0, int lane, int dt) {
   const int p = lane & 15, seg = dt * 2 + ((lane >> 4) & 1);
   const int row = key0 + (p >> 2);
-  const char* a = vt + row * 128 + ((seg ^ (((row >> 1) & 1) << 1)) << 5) + ((p & 3) << 3);
-  const s16x4 r = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)a);
-  return __builtin_bit_cast(u32x2, r);
+  return ds_read_tr16(vt + row * 128 + ((seg ^ (((row >> 1) & 1) << 1)) << 5) + ((p & 3) << 3));
 }
 template <typename T> __device__ __forceinline__ u32x4 load_vt_chunk16(const char* vt, int cc, int lane, int dt) {
   const int g = lane >> 5;
-  const u32x2 a = tr_quad(vt, 16 * cc + 4 * g, lane, dt);      // regs 8cc..8cc+3
-  const u32x2 b = tr_quad(vt, 16 * cc + 8 + 4 * g, lane, dt);  // regs 8cc+4..8cc+7
+  const u32x2 a = tr_quad_v(vt, 16 * cc + 4 * g, lane, dt);      // regs 8cc..8cc+3
+  const u32x2 b = tr_quad_v(vt, 16 * cc + 8 + 4 * g, lane, dt);  // regs 8cc+4..8cc+7
   const uint32_t ax = a.x, ay = a.y, bx = b.x, by = b.y;
   return mk4(ax, ay, bx, by);
 }
 template <> __device__ __forceinline__ u32x4 load_vt_chunk<bf16_t>(const char* vt, int cc, int lane, int dt) { return load_vt_chunk16<bf16_t>(vt, cc, lane, dt); }
 template <> __device__ __forceinline__ u32x4 load_vt_chunk<f16_t>(const char* vt, int cc, int lane, int dt) { return load_vt_chunk16<f16_t>(vt, cc, lane, dt); }
-
-// store 4 consecutive outputs d0..d0+3 of one query row
-template <typename T> __device__ __forceinline__ void store_quad(T* dst, const float* v) {
-  if constexpr (sizeof(T) == 4) {
-    *(float4*)dst = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-    u32x2 u;
-    u.x = pack2(v[0], v[1], (T*)0);
-    u.y = pack2(v[2], v[3], (T*)0);
-    *(u32x2*)dst = u;
-  }
-}
 
 // softmax over NKT key tiles held in C layout.  `bias4(kt, rq)` returns the additive fp32 bias of the
 // four keys of accumulator registers 4rq..4rq+3 (-inf masks a key).  p is normalised in place;
@@ -140,7 +114,7 @@ __device__ __forceinline__ float softmax_tiles(f32x16 (&s)[NKT], float scale, Bi
 // O^T (2 d-tiles) += V^T P^T over NKT key tiles; vt points at key 0 of the LDS V image
 template <typename T, int NKT>
 __device__ __forceinline__ void pv_tiles(f32x16 (&o)[2], const f32x16 (&p)[NKT], const char* vt, int lane) {
-  typedef AttnCfg<T> C;
+  typedef TileCfg<T> C;
 #pragma unroll
   for (int kt = 0; kt < NKT; ++kt) {
 #pragma unroll
@@ -171,7 +145,7 @@ __device__ __forceinline__ void pv_tiles(f32x16 (&o)[2], const f32x16 (&p)[NKT],
 #endif
 template <typename T, int NKT, int PDV = 3>
 __device__ __forceinline__ void pv_tiles_pipelined(f32x16 (&o)[2], const f32x16 (&p)[NKT], const char* vt, int lane) {
-  typedef AttnCfg<T> C;
+  typedef TileCfg<T> C;
   constexpr int NSTEP = NKT * C::CPT * 2;
   u32x4 ring[PDV];
   auto vchunk = [&](int i) __attribute__((always_inline)) {
@@ -196,25 +170,13 @@ __device__ __forceinline__ void pv_tiles_pipelined(f32x16 (&o)[2], const f32x16 
   }
 }
 
-template <typename T>
-__device__ __forceinline__ void store_o(T* out_row, const f32x16 (&o)[2], int lane) {
-  const int g = lane >> 5;
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int rq = 0; rq < 4; ++rq) {
-      const float v[4] = {o[dt][4 * rq], o[dt][4 * rq + 1], o[dt][4 * rq + 2], o[dt][4 * rq + 3]};
-      store_quad<T>(out_row + dt * 32 + 8 * rq + 4 * g, v);
-    }
-}
-
 // ================================================================================================
 // full attention: grid = batch * H workgroups of 256 threads
 template <typename T, int NKT>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(const T* __restrict__ qkv, T* __restrict__ out, int L, int H, float scale,
                                                        const float* __restrict__ key_bias, float* __restrict__ lse, float drop_p,
                                                        uint32_t drop_seed) {
-  typedef AttnCfg<T> C;
+  typedef TileCfg<T> C;
   constexpr int LP = NKT * 32;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* Ks = smem;
@@ -280,7 +242,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const T* __restrict__ qkv
 #pragma unroll
       for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
     pv_tiles<T, NKT>(o, s, Vs, lane);
-    if (q < L) store_o<T>(out + ((int64_t)b * L + q) * H * HD + h * HD, o, lane);
+    if (q < L) store_row64<T>(out + ((int64_t)b * L + q) * H * HD + h * HD, o, lane);
   }
 }
 
@@ -296,7 +258,6 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const T* __restrict__ qkv
 //  * the next query tile's Q fragments are prefetched under the current tile's softmax;
 //  * O^T is transposed through 4 KiB of wave-private LDS so that a row's 128 bytes leave in 16-byte stores.
 __device__ u32x4 g_attn_zero[4];
-constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
 
 // The precise CLS query (round 4: alpro_amd.config.cls_precise; stand-alone form: cls_precise.hip alpro_attn_cls_fwd) -- round 6 form.  The
 // CLS token's fp32 q row is carried THROUGH the 16-bit MFMA path as NS extra query columns whose values add up to it: x = p0 + p1 / C1
@@ -742,7 +703,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_kernel(const T* __restrict_
 template <typename T>
 __global__ __launch_bounds__(256) void attn_temporal_fwd_kernel(const T* __restrict__ qkv, T* __restrict__ out, int64_t rows, int Tn,
                                                                 int H, float scale, int64_t units, float* __restrict__ lse) {
-  typedef AttnCfg<T> C;
+  typedef TileCfg<T> C;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   char* Vs = smem + wave * 32 * C::RB;
@@ -792,7 +753,7 @@ __global__ __launch_bounds__(256) void attn_temporal_fwd_kernel(const T* __restr
 #pragma unroll
       for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
     pv_tiles<T, 1>(o, s, Vs, lane);
-    if (active && r0 + ql < rows) store_o<T>(out + (r0 + ql) * H * HD + h * HD, o, lane);
+    if (active && r0 + ql < rows) store_row64<T>(out + (r0 + ql) * H * HD + h * HD, o, lane);
   }
 }
 
@@ -891,11 +852,9 @@ __global__ __launch_bounds__(256, 2) void attn_temporal_fwd16_kernel(const T* __
 template <typename T, int NKT>
 int launch_attn(const void* qkv, void* out, int batch, int L, int H, float scale, const float* key_bias, float* lse, float drop_p,
                 uint32_t drop_seed, hipStream_t st) {
-  const size_t lds = 2 * (size_t)NKT * 32 * AttnCfg<T>::RB + (size_t)NKT * 32 * sizeof(float);
-  static DeviceOnce attr_once;
-  attr_once.run([&] {
-    (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<T, NKT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  });
+  const size_t lds = 2 * (size_t)NKT * 32 * TileCfg<T>::RB + (size_t)NKT * 32 * sizeof(float);
+  static DeviceOnce once;
+  set_lds_once(once, attn_fwd_kernel<T, NKT>, lds);
   hipLaunchKernelGGL((attn_fwd_kernel<T, NKT>), dim3(batch * H), dim3(256), lds, st, (const T*)qkv, (T*)out, L, H, scale, key_bias, lse, drop_p, drop_seed);
   return check_launch("alpro_attn_fwd");
 }
@@ -904,12 +863,10 @@ template <typename T, int NKT, bool HAS_BIAS>
 int launch_attn16(const void* qkv, void* out, int batch, int L, int H, float scale, const float* key_bias, float* lse, float drop_p,
                   uint32_t drop_seed, const float* cls_q, int cls_group, float* cls_out, hipStream_t st) {
   const size_t lds = 2 * (size_t)NKT * 32 * 128 + 4 * (NKT == 8 ? 2048 : 4096) + (size_t)NKT * 32 * sizeof(float);
-  static DeviceOnce attr_once;
-  attr_once.run([&] {
-    (void)hipFuncSetAttribute((const void*)attn_fwd16_kernel<T, NKT, HAS_BIAS, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void*)attn_fwd16_kernel<T, NKT, HAS_BIAS, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void*)attn_fwd16_kernel<T, NKT, HAS_BIAS, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  });
+  static DeviceOnce once_plain, once_cls, once_cls_drop;
+  set_lds_once(once_plain, attn_fwd16_kernel<T, NKT, HAS_BIAS, false, false>, lds);
+  set_lds_once(once_cls, attn_fwd16_kernel<T, NKT, HAS_BIAS, true, false>, lds);
+  set_lds_once(once_cls_drop, attn_fwd16_kernel<T, NKT, HAS_BIAS, true, true>, lds);
 #define ALPRO_ATTN16_GO(CLS_, DROP_)                                                                                                                     \
   hipLaunchKernelGGL((attn_fwd16_kernel<T, NKT, HAS_BIAS, CLS_, DROP_>), dim3(batch * H), dim3(256), lds, st, (const T*)qkv, (T*)out, L, H, scale, key_bias, lse, drop_p, \
                      drop_seed, get_option(OPT_ATTN_ORDER), cls_q, cls_group, cls_out)
@@ -977,11 +934,9 @@ extern "C" int alpro_attn_temporal_fwd(const void* qkv, void* out, int dtype, in
   if (grid > 256 * 8) grid = 256 * 8;
   if (dtype != ALPRO_F32) {  // 16-bit storage: DMA-staged wave-private tiles
     const size_t lds16 = 4 * 3 * 4096;
-    static DeviceOnce attr_once;
-    attr_once.run([&] {
-      (void)hipFuncSetAttribute((const void*)attn_temporal_fwd16_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16);
-      (void)hipFuncSetAttribute((const void*)attn_temporal_fwd16_kernel<f16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16);
-    });
+    static DeviceOnce once_bf16, once_f16;
+    set_lds_once(once_bf16, attn_temporal_fwd16_kernel<bf16_t>, lds16);
+    set_lds_once(once_f16, attn_temporal_fwd16_kernel<f16_t>, lds16);
     if (grid > 512) grid = 512;  // 2 workgroups per CU, units handed out grid-stride
     if (dtype == ALPRO_BF16)
       hipLaunchKernelGGL(attn_temporal_fwd16_kernel<bf16_t>, dim3((unsigned)grid), dim3(256), lds16, (hipStream_t)stream, (const bf16_t*)qkv, (bf16_t*)out, rows, T, H, scale, units, lse);

@@ -9,87 +9,17 @@
 //   phase 2 (Q, dO tiles re-staged into the same LDS; one 32-key tile per wave; lane = key)
 //       S = Q K^T, dP = dO V^T                      A = rows of Q / dO, B = K / V rows of the key tile (registers)
 //       dV^T += dO^T P,  dK^T += Q^T dS             A = dO^T / Q^T via transpose reads, B = P / dS from registers
-// One LDS swizzle serves both access kinds for 16-bit tiles: chunk ^= (bit1(row) << 2 | (row >> 2) & 3) is a bijection
-// of (row >> 1) & 7 (conflict-free ds_read_b128 fragments) AND moves rows r, r+2 into different 64-byte windows
-// (conflict-free 4-row transpose gathers).  The temporal variant treats 32 consecutive tokens as one tile with a
-// block-diagonal group mask (one wave per workgroup).
+// The LDS tiles are U tiles (attn_tile.hpp): one swizzle serves the row reads and the transpose reads.  The temporal variant
+// treats 32 consecutive tokens as one tile with a block-diagonal group mask (one wave per workgroup).
 #include "common.hpp"
+#include "attn_tile.hpp"
 
 namespace alpro {
 namespace {
 
-constexpr int HD = 64;
-
-template <typename T> struct BCfg {
-  static constexpr int E = sizeof(T);
-  static constexpr int CN = 16 / E;
-  static constexpr int RB = HD * E;
-  static constexpr int CPR = RB / 16;
-  static constexpr int KS = CPR / 2;
-  static constexpr int CPT = 16 / CN;
-};
-
-template <typename T> __device__ __forceinline__ int u_swz(int row, int chunk) {
-  if (BCfg<T>::CPR == 8) return chunk ^ ((((row >> 1) & 1) << 2) | ((row >> 2) & 3));
-  return chunk ^ (row & 15);
-}
-template <typename T> __device__ __forceinline__ int tile_off(int row, int chunk) { return row * BCfg<T>::RB + (u_swz<T>(row, chunk) << 4); }
-
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-
-// transposed A-operand chunk: element (k, i) = tile[row0 + krow(cc, g, k)][dt*32 + (lane & 31)], the k order being
-// the accumulator-register order of the matching B operand (regs cc*CN .. cc*CN+CN-1).
-template <typename T> __device__ __forceinline__ u32x4 load_t_chunk(const char* tile, int row0, int cc, int lane, int dt);
-template <> __device__ __forceinline__ u32x4 load_t_chunk<float>(const char* tile, int row0, int cc, int lane, int dt) {
-  const int d = dt * 32 + (lane & 31), r = row0 + 8 * cc + 4 * (lane >> 5);
-  uint32_t v[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) v[e] = *(const uint32_t*)(tile + tile_off<float>(r + e, d >> 2) + ((d & 3) << 2));
-  return mk4(v[0], v[1], v[2], v[3]);
-}
-__device__ __forceinline__ u32x2 tr_quad_u(const char* tile, int krow0, int lane, int dt) {
-  const int p = lane & 15, seg = dt * 2 + ((lane >> 4) & 1);
-  const int row = krow0 + (p >> 2);
-  const int ch = seg * 2 + ((p >> 1) & 1);
-  const char* a = tile + row * 128 + ((ch ^ ((((row >> 1) & 1) << 2) | ((row >> 2) & 3))) << 4) + ((p & 1) << 3);
-  const s16x4 r = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)a);
-  return __builtin_bit_cast(u32x2, r);
-}
-template <typename T> __device__ __forceinline__ u32x4 load_t_chunk16(const char* tile, int row0, int cc, int lane, int dt) {
-  const int g = lane >> 5;
-  const u32x2 a = tr_quad_u(tile, row0 + 16 * cc + 4 * g, lane, dt);
-  const u32x2 b = tr_quad_u(tile, row0 + 16 * cc + 8 + 4 * g, lane, dt);
-  const uint32_t ax = a.x, ay = a.y, bx = b.x, by = b.y;
-  return mk4(ax, ay, bx, by);
-}
-template <> __device__ __forceinline__ u32x4 load_t_chunk<bf16_t>(const char* tile, int row0, int cc, int lane, int dt) { return load_t_chunk16<bf16_t>(tile, row0, cc, lane, dt); }
-template <> __device__ __forceinline__ u32x4 load_t_chunk<f16_t>(const char* tile, int row0, int cc, int lane, int dt) { return load_t_chunk16<f16_t>(tile, row0, cc, lane, dt); }
-
-template <typename T> __device__ __forceinline__ void store_quad_b(T* dst, const float* v) {
-  if constexpr (sizeof(T) == 4) {
-    *(float4*)dst = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-    u32x2 u;
-    u.x = pack2(v[0], v[1], (T*)0);
-    u.y = pack2(v[2], v[3], (T*)0);
-    *(u32x2*)dst = u;
-  }
-}
-// accumulator pair (2 d-tiles, C layout: column = token of this lane, rows = d) -> one token row of 64 values
-template <typename T> __device__ __forceinline__ void store_row64(T* row, const f32x16 (&o)[2], int lane) {
-  const int g = lane >> 5;
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int rq = 0; rq < 4; ++rq) {
-      const float v[4] = {o[dt][4 * rq], o[dt][4 * rq + 1], o[dt][4 * rq + 2], o[dt][4 * rq + 3]};
-      store_quad_b<T>(row + dt * 32 + 8 * rq + 4 * g, v);
-    }
-}
-
 template <typename T>
 __device__ __forceinline__ void stage_tile(char* tile, const T* src, int64_t ld, int rows_valid, int LP, int tid, int nthreads) {
-  typedef BCfg<T> C;
+  typedef TileCfg<T> C;
   for (int c = tid; c < LP * C::CPR; c += nthreads) {
     const int row = c / C::CPR, ch = c - row * C::CPR;
     u32x4 v = mk4(0, 0, 0, 0);
@@ -103,7 +33,7 @@ __global__ __launch_bounds__(NW * 64) void attn_bwd_kernel(const T* __restrict__
                                                            const float* __restrict__ lse, T* __restrict__ dqkv, int L, int H, float scale,
                                                            const float* __restrict__ key_bias, int Tn, int64_t total_rows, float drop_p,
                                                            uint32_t drop_seed) {
-  typedef BCfg<T> C;
+  typedef TileCfg<T> C;
   constexpr int LP = NKT * 32;
   constexpr int NT = NW * 64;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -288,7 +218,6 @@ __global__ __launch_bounds__(NW * 64) void attn_bwd_kernel(const T* __restrict__
 //  * dQ, dK, dV tiles are transposed through 4 KiB of wave-private LDS and leave as 16-byte row stores;
 //  * <= 256 registers and ~76 KiB of LDS: two workgroups per CU.
 __device__ u32x4 g_bwd_zero[4];
-constexpr float LOG2E_B = 1.4426950408889634f;
 
 // wave-private transpose: accumulator pair (column = token of this lane, rows = d) -> 32 row-major 128-byte rows.
 // HALF: 2 KiB of staging instead of 4 -- the two 32-wide d halves go one after the other as 64-byte row pieces (used where
@@ -363,10 +292,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd16_kernel(const T* __restrict_
   const uint32_t dth = drop_thresh24(drop_p);
   const float dks = drop_seed ? 1.0f / (1.0f - drop_p) : 1.0f;
   const uint64_t dbase = ((uint64_t)b * H + h) * (uint64_t)L;  // + q, then * L + key
-  const float sl = scale * LOG2E_B;
+  const float sl = scale * LOG2E;
   for (int c = tid; c < LP; c += 256) {
-    Bs[c] = c < L ? (HAS_BIAS ? key_bias[(int64_t)b * L + c] * LOG2E_B : 0.f) : -INFINITY;
-    Ls[c] = c < L ? -lse_b[c] * LOG2E_B : -INFINITY;
+    Bs[c] = c < L ? (HAS_BIAS ? key_bias[(int64_t)b * L + c] * LOG2E : 0.f) : -INFINITY;
+    Ls[c] = c < L ? -lse_b[c] * LOG2E : -INFINITY;
   }
   const uint32_t a_lds = lds_addr_of(tA), b_lds = lds_addr_of(tB);
   const char* zero = (const char*)g_bwd_zero;
@@ -634,14 +563,14 @@ __global__ __launch_bounds__(512) void attn_bwd16k_kernel(const T* __restrict__ 
   const uint32_t dth = drop_thresh24(drop_p);
   const float dks = drop_seed ? 1.0f / (1.0f - drop_p) : 1.0f;
   const uint64_t dbase = ((uint64_t)b * H + h) * (uint64_t)L;  // + q, then * L + key
-  const float sl = scale * LOG2E_B;
+  const float sl = scale * LOG2E;
   const int g = lane >> 5, ql = lane & 31;
   const int ntile = (L + 31) >> 5;           // >= 5 (dispatch)
   const bool active = wave < ntile;          // wave-uniform: this wave owns key tile `wave`
   ALPRO_TS(0);
   for (int c = tid; c < LP; c += 512) {
-    Bs[c] = c < L ? (key_bias ? key_bias[(int64_t)b * L + c] * LOG2E_B : 0.f) : -INFINITY;
-    Ls[c] = c < L ? -lse_b[c] * LOG2E_B : -INFINITY;
+    Bs[c] = c < L ? (key_bias ? key_bias[(int64_t)b * L + c] * LOG2E : 0.f) : -INFINITY;
+    Ls[c] = c < L ? -lse_b[c] * LOG2E : -INFINITY;
   }
   {  // K, Q, dO rows -> LDS images (chunk ^ (bit1(row) << 2 | (row >> 2) & 3)), 1 KiB DMA pieces
     const uint32_t k_lds = lds_addr_of(tK), q_lds = lds_addr_of(tQ), d_lds = lds_addr_of(tD);
@@ -706,8 +635,7 @@ __global__ __launch_bounds__(512) void attn_bwd16k_kernel(const T* __restrict__ 
     const int p = lane & 15, cb = (lane >> 4) & 1;
     const int row = k0 + (p >> 2);
     const char* a = img + row * 64 + ((((cb << 2) | (p & 3)) ^ ((row >> 2) & 7)) << 3);
-    const s16x4 r = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)a);
-    return __builtin_bit_cast(u32x2, r);
+    return ds_read_tr16(a);
   };
 #pragma unroll 1
   for (int q0 = 0; q0 < ntile; q0 += RQ) {
@@ -853,7 +781,7 @@ __global__ __launch_bounds__(512) void attn_bwd16p_kernel(const T* __restrict__ 
   const int nu = (units - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;   // units of this workgroup: blockIdx + i * grid
   const int S = nu * NT;                                                           // steps
   const int64_t ldq = 3 * (int64_t)H * HD, ldo = (int64_t)H * HD;
-  const float sl = scale * LOG2E_B;
+  const float sl = scale * LOG2E;
   const uint32_t kb_lds = lds_addr_of(Kb), rg_lds = lds_addr_of(Rg);
   // Per-lane LDS offsets: four base values; every access is (base ^ constant) + wave-uniform base + constant.  The tile swizzles only
   // touch row bits 1..3 and XOR disjoint bit fields, so the per-chunk / per-row-block variants are single v_xor rematerialisations of the
@@ -875,13 +803,9 @@ __global__ __launch_bounds__(512) void attn_bwd16p_kernel(const T* __restrict__ 
   auto tro = [&](int h2, int dt) { return (tb ^ (((4 * dt) ^ (2 * h2)) << 4)) + h2 * 1024; };   // rows 8h + r0, 16-column segment 2dt + (lane >> 4 & 1)
   auto iw = [&](int cc, int h2) { return wb ^ ((4 * cc + 2 * h2) << 3); };
   auto ir = [&](int cc, int h2) { return (rb ^ ((4 * cc + 2 * h2) << 3)) + (16 * cc + 8 * h2) * 64; };
-  auto tr8 = [](const char* a) -> u32x2 {
-    const s16x4 r = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)a);
-    return __builtin_bit_cast(u32x2, r);
-  };
   // transposed A chunk of rows [rowbase, rowbase + 16) (rowbase a multiple of 16), d half dt (the chunk the other kernels' transposed-chunk loader returns)
   auto tr_chunk = [&](const char* tile, int rowbase, int dt) -> u32x4 {
-    const u32x2 x = tr8(tile + tro(0, dt) + rowbase * 128), y = tr8(tile + tro(1, dt) + rowbase * 128);
+    const u32x2 x = ds_read_tr16(tile + tro(0, dt) + rowbase * 128), y = ds_read_tr16(tile + tro(1, dt) + rowbase * 128);
     const uint32_t x0 = x.x, x1 = x.y, y0 = y.x, y1 = y.y;
     return mk4(x0, x1, y0, y1);
   };
@@ -973,7 +897,7 @@ __global__ __launch_bounds__(512) void attn_bwd16p_kernel(const T* __restrict__ 
     delta += __shfl_xor(delta, 32, 64);
     if (g == 0) {
       float* st = St + par * 64;
-      st[ql] = tx * 32 + ql < L ? -lse_v * LOG2E_B : -INFINITY;
+      st[ql] = tx * 32 + ql < L ? -lse_v * LOG2E : -INFINITY;
       st[32 + ql] = -delta * scale;
     }
   };
@@ -1024,7 +948,7 @@ __global__ __launch_bounds__(512) void attn_bwd16p_kernel(const T* __restrict__ 
     auto load_stage = [&](int kt, int st) {
 #pragma unroll
       for (int cc = 0; cc < 2; ++cc) {
-        const u32x2 lo = tr8(img0 + kt * IMG + ir(cc, 0)), hi = tr8(img0 + kt * IMG + ir(cc, 1));
+        const u32x2 lo = ds_read_tr16(img0 + kt * IMG + ir(cc, 0)), hi = ds_read_tr16(img0 + kt * IMG + ir(cc, 1));
         const uint32_t lx = lo.x, ly = lo.y, hx = hi.x, hy = hi.y;
         bv[st][cc] = mk4(lx, ly, hx, hy);
 #pragma unroll
@@ -1272,7 +1196,7 @@ __global__ __launch_bounds__(256, 2) void attn_temporal_bwd16_kernel(const T* __
   const char* zero = (const char*)g_bwd_zero;
   const int64_t ldq = 3 * (int64_t)H * HD, ldo = (int64_t)H * HD;
   const int g = lane >> 5, ql = lane & 31;
-  const float sl = scale * LOG2E_B;
+  const float sl = scale * LOG2E;
   const int qgrp = ql / Tn;
   for (int64_t unit = (int64_t)blockIdx.x * 4 + wave; unit < units; unit += (int64_t)gridDim.x * 4) {
     const int64_t chunk = unit / H;
@@ -1293,7 +1217,7 @@ __global__ __launch_bounds__(256, 2) void attn_temporal_bwd16_kernel(const T* __
       dma16(ok ? (const char*)src : zero, __builtin_amdgcn_readfirstlane(lds0 + 8192 + piece * 1024));
       dma16(ok ? (const char*)(dob + (int64_t)row * ldo + ch * 8) : zero, __builtin_amdgcn_readfirstlane(lds0 + 12288 + piece * 1024));
     }
-    if (lane < 32) Ls[lane] = lane < Le ? -lse[unit * 32 + lane] * LOG2E_B : -INFINITY;
+    if (lane < 32) Ls[lane] = lane < Le ? -lse[unit * 32 + lane] * LOG2E : -INFINITY;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     // ------------------------------------------------------------ phase 1: dQ (lane = query)
     u32x4 qf[4], dof[4];
@@ -1397,10 +1321,8 @@ template <typename T, int NKT, bool HAS_BIAS, bool DROP>
 int launch_bwd16(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int batch, int L, int H, float scale,
                  const float* key_bias, float dp, uint32_t ds, hipStream_t st) {
   const size_t lds = 2 * (size_t)NKT * 32 * 128 + 4 * (NKT == 8 ? 2048 : 4096) + 3 * (size_t)NKT * 32 * sizeof(float);
-  static DeviceOnce attr_once;
-  attr_once.run([&] {
-    (void)hipFuncSetAttribute((const void*)attn_bwd16_kernel<T, NKT, HAS_BIAS, DROP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  });
+  static DeviceOnce once;
+  set_lds_once(once, attn_bwd16_kernel<T, NKT, HAS_BIAS, DROP>, lds);
   hipLaunchKernelGGL((attn_bwd16_kernel<T, NKT, HAS_BIAS, DROP>), dim3((unsigned)(batch * H)), dim3(256), lds, st, (const T*)qkv, (const T*)out, (const T*)dout,
                      lse, (T*)dqkv, L, H, scale, key_bias, dp, ds, get_option(OPT_ATTN_ORDER));
   return check_launch("alpro_attn_bwd");
@@ -1411,10 +1333,8 @@ int launch_bwd16k(const void* qkv, const void* out, const void* dout, const floa
                   const float* key_bias, float dp, uint32_t ds, hipStream_t st) {
   constexpr int LP = NKT * 32;
   const size_t lds = 3 * (size_t)LP * 128 + (size_t)(NKT <= 7 ? 4 : 3) * NKT * 2048 + 3 * (size_t)LP * sizeof(float);
-  static DeviceOnce attr_once;
-  attr_once.run([&] {
-    (void)hipFuncSetAttribute((const void*)attn_bwd16k_kernel<T, NKT, DROP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  });
+  static DeviceOnce once;
+  set_lds_once(once, attn_bwd16k_kernel<T, NKT, DROP>, lds);
   hipLaunchKernelGGL((attn_bwd16k_kernel<T, NKT, DROP>), dim3((unsigned)(batch * H)), dim3(512), lds, st, (const T*)qkv, (const T*)out, (const T*)dout,
                      lse, (T*)dqkv, L, H, scale, key_bias, dp, ds, get_option(OPT_ATTN_ORDER));
   return check_launch("alpro_attn_bwd");
@@ -1425,10 +1345,8 @@ template <typename T>
 int launch_bwd16p(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int batch, int L, int H, float scale,
                   int flags, hipStream_t st) {
   const size_t lds = 2 * 7 * 4096 + 2 * 7 * 2048 + 5 * 3 * 4096 + (2 * 64 + 8 * 32) * sizeof(float);
-  static DeviceOnce attr_once;
-  attr_once.run([&] {
-    (void)hipFuncSetAttribute((const void*)attn_bwd16p_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  });
+  static DeviceOnce once;
+  set_lds_once(once, attn_bwd16p_kernel<T>, lds);
   const int units = batch * H;
   hipLaunchKernelGGL((attn_bwd16p_kernel<T>), dim3((unsigned)(units < 256 ? units : 256)), dim3(512), lds, st, (const T*)qkv, (const T*)out,
                      (const T*)dout, lse, (T*)dqkv, L, H, scale, units, flags);
@@ -1439,11 +1357,9 @@ int launch_bwd16p(const void* qkv, const void* out, const void* dout, const floa
 template <typename T, int NKT, int NW, bool GROUPED>
 int launch_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int64_t nblocks_b, int L, int H, float scale,
                const float* key_bias, int Tn, int64_t total_rows, float dp, uint32_t ds, hipStream_t st) {
-  const size_t lds = 2 * (size_t)NKT * 32 * BCfg<T>::RB + 3 * (size_t)NKT * 32 * sizeof(float);
-  static DeviceOnce attr_once;
-  attr_once.run([&] {
-    (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<T, NKT, NW, GROUPED>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  });
+  const size_t lds = 2 * (size_t)NKT * 32 * TileCfg<T>::RB + 3 * (size_t)NKT * 32 * sizeof(float);
+  static DeviceOnce once;
+  set_lds_once(once, attn_bwd_kernel<T, NKT, NW, GROUPED>, lds);
   hipLaunchKernelGGL((attn_bwd_kernel<T, NKT, NW, GROUPED>), dim3((unsigned)(nblocks_b * H)), dim3(NW * 64), lds, st, (const T*)qkv, (const T*)out,
                      (const T*)dout, lse, (T*)dqkv, L, H, scale, key_bias, Tn, total_rows, dp, ds);
   return check_launch("alpro_attn_bwd");
@@ -1518,11 +1434,9 @@ extern "C" int alpro_attn_temporal_bwd(const void* qkv, const void* out, const v
     int64_t grid = (units + 3) / 4;
     if (grid > 512) grid = 512;
     const size_t lds = 4 * (4 * 4096 + 256);
-    static DeviceOnce attr_once;
-    attr_once.run([&] {
-      (void)hipFuncSetAttribute((const void*)attn_temporal_bwd16_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      (void)hipFuncSetAttribute((const void*)attn_temporal_bwd16_kernel<f16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    });
+    static DeviceOnce once_bf16, once_f16;
+    set_lds_once(once_bf16, attn_temporal_bwd16_kernel<bf16_t>, lds);
+    set_lds_once(once_f16, attn_temporal_bwd16_kernel<f16_t>, lds);
     if (dtype == ALPRO_BF16) {
       hipLaunchKernelGGL(attn_temporal_bwd16_kernel<bf16_t>, dim3((unsigned)grid), dim3(256), lds, (hipStream_t)stream, (const bf16_t*)qkv, (const bf16_t*)dout, lse,
                          (bf16_t*)dqkv, rows, T, H, scale, units);

@@ -13,84 +13,20 @@
 //             dK/dV one workgroup per 4 key tiles, sweeping Q / dO blocks:   dV^T += dO^T P,  dK^T += Q^T dS
 //             P is recomputed from Q, K and lse; delta = rowsum(dO o O) is formed on the fly (per query tile in the dQ kernel, per staged query
 //             block in the dK/dV kernel) -- O already carries the dropout mask, so the identity holds with dropout too.
-// LDS images use one swizzle for row reads (ds_read_b128) and transposed reads (ds_read_b64_tr_b16), as attention_bwd.hip does.
+// LDS images are U tiles (attn_tile.hpp): one swizzle for row reads (ds_read_b128) and transposed reads (ds_read_b64_tr_b16).
 #include "common.hpp"
+#include "attn_tile.hpp"
 
 namespace alpro {
 namespace {
 
-constexpr int HD = 64;
 constexpr int NW = 4;     // waves per workgroup = 32-row tiles owned per workgroup
 constexpr int KB = 64;    // rows per staged block (two 32-row tiles)
-constexpr float LOG2E = 1.4426950408889634f;
-constexpr float LN2 = 0.69314718055994531f;
 
-template <typename T> struct LCfg {
-  static constexpr int E = sizeof(T);
-  static constexpr int CN = 16 / E;         // elements per 16-byte chunk
-  static constexpr int RB = HD * E;         // bytes per head row
-  static constexpr int CPR = RB / 16;       // chunks per head row (8 or 16)
-  static constexpr int KS = CPR / 2;        // MFMA chunk-steps over head_dim
-  static constexpr int CPT = 16 / CN;       // P chunks per 32-row tile
-  static constexpr int NLD = KB * CPR / 256;  // chunks of one staged matrix per thread
-  static constexpr int IMG = KB * RB;       // bytes of one staged matrix
+template <typename T> struct LCfg : TileCfg<T> {
+  static constexpr int NLD = KB * TileCfg<T>::CPR / 256;  // chunks of one staged matrix per thread
+  static constexpr int IMG = KB * TileCfg<T>::RB;         // bytes of one staged matrix
 };
-
-// 16-bit rows (128 B): chunk ^= bit1(row) << 2 | (row >> 2) & 3 -- conflict-free ds_read_b128 row fragments AND 4-row transpose gathers.
-template <typename T> __device__ __forceinline__ int l_off(int row, int chunk) {
-  if (LCfg<T>::CPR == 8) return row * 128 + ((chunk ^ ((((row >> 1) & 1) << 2) | ((row >> 2) & 3))) << 4);
-  return row * 256 + ((chunk ^ (row & 15)) << 4);
-}
-
-// transposed A-operand chunk: element (k, i) = tile[row0 + krow(cc, g, k)][dt*32 + (lane & 31)], k in the accumulator-register order of the
-// matching B operand (regs cc*CN .. cc*CN+CN-1)
-template <typename T> __device__ __forceinline__ u32x4 load_t_chunk(const char* tile, int row0, int cc, int lane, int dt);
-template <> __device__ __forceinline__ u32x4 load_t_chunk<float>(const char* tile, int row0, int cc, int lane, int dt) {
-  const int d = dt * 32 + (lane & 31), r = row0 + 8 * cc + 4 * (lane >> 5);
-  uint32_t v[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) v[e] = *(const uint32_t*)(tile + l_off<float>(r + e, d >> 2) + ((d & 3) << 2));
-  return mk4(v[0], v[1], v[2], v[3]);
-}
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-// ds_read_b64_tr_b16: within each 16-lane group, lane l receives element (l & 3) of the 8-byte piece addressed by lane (l >> 2) + 4j
-__device__ __forceinline__ u32x2 tr_quad(const char* tile, int krow0, int lane, int dt) {
-  const int p = lane & 15, seg = dt * 2 + ((lane >> 4) & 1);
-  const int row = krow0 + (p >> 2);
-  const int ch = seg * 2 + ((p >> 1) & 1);
-  const char* a = tile + row * 128 + ((ch ^ ((((row >> 1) & 1) << 2) | ((row >> 2) & 3))) << 4) + ((p & 1) << 3);
-  const s16x4 r = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)a);
-  return __builtin_bit_cast(u32x2, r);
-}
-template <typename T> __device__ __forceinline__ u32x4 load_t_chunk16(const char* tile, int row0, int cc, int lane, int dt) {
-  const int g = lane >> 5;
-  const u32x2 a = tr_quad(tile, row0 + 16 * cc + 4 * g, lane, dt);
-  const u32x2 b = tr_quad(tile, row0 + 16 * cc + 8 + 4 * g, lane, dt);
-  const uint32_t ax = a.x, ay = a.y, bx = b.x, by = b.y;
-  return mk4(ax, ay, bx, by);
-}
-template <> __device__ __forceinline__ u32x4 load_t_chunk<bf16_t>(const char* tile, int row0, int cc, int lane, int dt) { return load_t_chunk16<bf16_t>(tile, row0, cc, lane, dt); }
-template <> __device__ __forceinline__ u32x4 load_t_chunk<f16_t>(const char* tile, int row0, int cc, int lane, int dt) { return load_t_chunk16<f16_t>(tile, row0, cc, lane, dt); }
-
-// accumulator pair (2 d-tiles, C layout: column = row of this lane, rows = d) -> one row of 64 values
-template <typename T> __device__ __forceinline__ void store_row64(T* row, const f32x16 (&o)[2], int lane) {
-  const int g = lane >> 5;
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int rq = 0; rq < 4; ++rq) {
-      const float v[4] = {o[dt][4 * rq], o[dt][4 * rq + 1], o[dt][4 * rq + 2], o[dt][4 * rq + 3]};
-      T* dst = row + dt * 32 + 8 * rq + 4 * g;
-      if constexpr (sizeof(T) == 4) {
-        *(float4*)dst = make_float4(v[0], v[1], v[2], v[3]);
-      } else {
-        u32x2 u;
-        u.x = pack2(v[0], v[1], (T*)0);
-        u.y = pack2(v[2], v[3], (T*)0);
-        *(u32x2*)dst = u;
-      }
-    }
-}
 
 // (unit = sequence * H + head, group of NW tiles) of this workgroup.  Workgroups go to the 8 XCDs round-robin; when the grid is a multiple of 8,
 // XCD x gets the contiguous id range [x, x+1) * grid/8, so the groups of one (sequence, head) -- which read the same K / V (Q / dO) blocks --
@@ -123,8 +59,8 @@ template <typename T> struct BlockPair {
 #pragma unroll
     for (int i = 0; i < C::NLD; ++i) {
       const int c = tid + 256 * i, row = c / C::CPR, ch = c - row * C::CPR;
-      *(u32x4*)(ia + l_off<T>(row, ch)) = a[i];
-      *(u32x4*)(ib + l_off<T>(row, ch)) = b[i];
+      *(u32x4*)(ia + tile_off<T>(row, ch)) = a[i];
+      *(u32x4*)(ib + tile_off<T>(row, ch)) = b[i];
     }
   }
 };
@@ -198,7 +134,7 @@ __global__ __launch_bounds__(256) void attn_long_fwd_kernel(const T* __restrict_
           for (int r = 0; r < 16; ++r) s[kt][r] = 0.f;
           const int krow = kt * 32 + ql;
 #pragma unroll
-          for (int ks = 0; ks < C::KS; ++ks) mma_chunk<T>(s[kt], *(const u32x4*)(Ks + l_off<T>(krow, 2 * ks + g)), qf[ks]);
+          for (int ks = 0; ks < C::KS; ++ks) mma_chunk<T>(s[kt], *(const u32x4*)(Ks + tile_off<T>(krow, 2 * ks + g)), qf[ks]);
         }
       }
       float mb = -INFINITY;
@@ -435,8 +371,8 @@ __global__ __launch_bounds__(256) void attn_long_dq_kernel(const T* __restrict__
           const int krow = kt * 32 + ql;
 #pragma unroll
           for (int ks = 0; ks < C::KS; ++ks) {
-            mma_chunk<T>(s, *(const u32x4*)(Ks + l_off<T>(krow, 2 * ks + g)), qf[ks]);
-            mma_chunk<T>(dp, *(const u32x4*)(Vs + l_off<T>(krow, 2 * ks + g)), dof[ks]);
+            mma_chunk<T>(s, *(const u32x4*)(Ks + tile_off<T>(krow, 2 * ks + g)), qf[ks]);
+            mma_chunk<T>(dp, *(const u32x4*)(Vs + tile_off<T>(krow, 2 * ks + g)), dof[ks]);
           }
 #pragma unroll
           for (int rq = 0; rq < 4; ++rq) {
@@ -566,8 +502,8 @@ __global__ __launch_bounds__(256) void attn_long_dkv_kernel(const T* __restrict_
           const int qrow = qt * 32 + ql;
 #pragma unroll
           for (int ks = 0; ks < C::KS; ++ks) {
-            mma_chunk<T>(s, *(const u32x4*)(Qs + l_off<T>(qrow, 2 * ks + g)), kf[ks]);
-            mma_chunk<T>(dp, *(const u32x4*)(Os + l_off<T>(qrow, 2 * ks + g)), vf[ks]);
+            mma_chunk<T>(s, *(const u32x4*)(Qs + tile_off<T>(qrow, 2 * ks + g)), kf[ks]);
+            mma_chunk<T>(dp, *(const u32x4*)(Os + tile_off<T>(qrow, 2 * ks + g)), vf[ks]);
           }
 #pragma unroll
           for (int rq = 0; rq < 4; ++rq) {
@@ -612,10 +548,6 @@ __global__ __launch_bounds__(256) void attn_long_dkv_kernel(const T* __restrict_
     store_row64<T>(dqkv + ((int64_t)b * L + key) * ldq + H * HD + h * HD, dk, lane);
     store_row64<T>(dqkv + ((int64_t)b * L + key) * ldq + 2 * H * HD + h * HD, dv, lane);
   }
-}
-
-template <typename K> void set_lds_once(DeviceOnce& once, K* kern, size_t lds) {
-  once.run([&] { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); });
 }
 
 template <typename T>

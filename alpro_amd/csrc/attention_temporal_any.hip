@@ -14,83 +14,17 @@
 //             dQ     lane = query of the unit, over the window's keys:    dS^T = P^T o (dP^T - delta) * scale,  dQ^T += K^T dS^T
 //             dK/dV  lane = key of the unit, over the window's queries:   dV^T += dO^T P,  dK^T += Q^T dS
 //             P is recomputed from Q, K and lse; delta = rowsum(dO o O) -- from registers for the unit's queries, while staging for the window's.
-// MFMA forms: 32x32x16 (bf16 / f16) and 32x32x2 f32, as in the other attention kernels.  LDS images use the row / transpose swizzle of
-// attention_long.hip.
+// MFMA forms: 32x32x16 (bf16 / f16) and 32x32x2 f32, as in the other attention kernels.  LDS images are U tiles (attn_tile.hpp).
 #include "common.hpp"
+#include "attn_tile.hpp"
 
 namespace alpro {
 namespace {
 
-constexpr int HD = 64;
-constexpr float LOG2E = 1.4426950408889634f;
-constexpr float LN2 = 0.69314718055994531f;
-
-template <typename T> struct TCfg {
-  static constexpr int E = sizeof(T);
-  static constexpr int CN = 16 / E;          // elements per 16-byte chunk
-  static constexpr int RB = HD * E;          // bytes per head row
-  static constexpr int CPR = RB / 16;        // chunks per head row (8 or 16)
-  static constexpr int KS = CPR / 2;         // MFMA chunk-steps over head_dim
-  static constexpr int CPT = 16 / CN;        // P chunks per 32-row tile
-  static constexpr int NLD = 32 * CPR / 64;  // chunks of one staged 32-row tile per lane
-  static constexpr int IMG = 32 * RB;        // bytes of one staged tile
+template <typename T> struct TCfg : TileCfg<T> {
+  static constexpr int NLD = 32 * TileCfg<T>::CPR / 64;  // chunks of one staged 32-row tile per lane
+  static constexpr int IMG = 32 * TileCfg<T>::RB;        // bytes of one staged tile
 };
-
-// 16-bit rows (128 B): chunk ^= bit1(row) << 2 | (row >> 2) & 3 -- conflict-free ds_read_b128 row fragments AND 4-row transpose gathers.
-template <typename T> __device__ __forceinline__ int l_off(int row, int chunk) {
-  if (TCfg<T>::CPR == 8) return row * 128 + ((chunk ^ ((((row >> 1) & 1) << 2) | ((row >> 2) & 3))) << 4);
-  return row * 256 + ((chunk ^ (row & 15)) << 4);
-}
-
-// transposed A-operand chunk: element (k, i) = tile[krow(cc, g, k)][dt*32 + (lane & 31)], k in the accumulator-register order of the matching
-// B operand (regs cc*CN .. cc*CN+CN-1)
-template <typename T> __device__ __forceinline__ u32x4 load_t_chunk(const char* tile, int cc, int lane, int dt);
-template <> __device__ __forceinline__ u32x4 load_t_chunk<float>(const char* tile, int cc, int lane, int dt) {
-  const int d = dt * 32 + (lane & 31), r = 8 * cc + 4 * (lane >> 5);
-  uint32_t v[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) v[e] = *(const uint32_t*)(tile + l_off<float>(r + e, d >> 2) + ((d & 3) << 2));
-  return mk4(v[0], v[1], v[2], v[3]);
-}
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-// ds_read_b64_tr_b16: within each 16-lane group, lane l receives element (l & 3) of the 8-byte piece addressed by lane (l >> 2) + 4j
-__device__ __forceinline__ u32x2 tr_quad(const char* tile, int krow0, int lane, int dt) {
-  const int p = lane & 15, seg = dt * 2 + ((lane >> 4) & 1);
-  const int row = krow0 + (p >> 2);
-  const int ch = seg * 2 + ((p >> 1) & 1);
-  const char* a = tile + row * 128 + ((ch ^ ((((row >> 1) & 1) << 2) | ((row >> 2) & 3))) << 4) + ((p & 1) << 3);
-  const s16x4 r = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)a);
-  return __builtin_bit_cast(u32x2, r);
-}
-template <typename T> __device__ __forceinline__ u32x4 load_t_chunk16(const char* tile, int cc, int lane, int dt) {
-  const int g = lane >> 5;
-  const u32x2 a = tr_quad(tile, 16 * cc + 4 * g, lane, dt);
-  const u32x2 b = tr_quad(tile, 16 * cc + 8 + 4 * g, lane, dt);
-  const uint32_t ax = a.x, ay = a.y, bx = b.x, by = b.y;
-  return mk4(ax, ay, bx, by);
-}
-template <> __device__ __forceinline__ u32x4 load_t_chunk<bf16_t>(const char* tile, int cc, int lane, int dt) { return load_t_chunk16<bf16_t>(tile, cc, lane, dt); }
-template <> __device__ __forceinline__ u32x4 load_t_chunk<f16_t>(const char* tile, int cc, int lane, int dt) { return load_t_chunk16<f16_t>(tile, cc, lane, dt); }
-
-// accumulator pair (2 d-tiles, C layout: column = row of this lane, rows = d) -> one row of 64 values
-template <typename T> __device__ __forceinline__ void store_row64(T* row, const f32x16 (&o)[2], int lane) {
-  const int g = lane >> 5;
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int rq = 0; rq < 4; ++rq) {
-      const float v[4] = {o[dt][4 * rq], o[dt][4 * rq + 1], o[dt][4 * rq + 2], o[dt][4 * rq + 3]};
-      T* dst = row + dt * 32 + 8 * rq + 4 * g;
-      if constexpr (sizeof(T) == 4) {
-        *(float4*)dst = make_float4(v[0], v[1], v[2], v[3]);
-      } else {
-        u32x2 u;
-        u.x = pack2(v[0], v[1], (T*)0);
-        u.y = pack2(v[2], v[3], (T*)0);
-        *(u32x2*)dst = u;
-      }
-    }
-}
 
 // The wave's LDS traffic so far has completed, and the compiler moves no memory access across this point.  A wave's DS operations execute
 // in order, so this is all the ordering a wave-private tile needs (write -> read and read -> next write).
@@ -108,7 +42,7 @@ template <typename T> __device__ __forceinline__ void stage_tile(char* tile, con
 #pragma unroll
   for (int i = 0; i < C::NLD; ++i) {
     const int c = lane + 64 * i, row = c / C::CPR, ch = c - row * C::CPR;
-    *(u32x4*)(tile + l_off<T>(row, ch)) = v[i];
+    *(u32x4*)(tile + tile_off<T>(row, ch)) = v[i];
   }
 }
 
@@ -194,7 +128,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 3 : 2) void tattn_any_fwd_ker
         for (int e = 0; e < C::CN; ++e) pv[e] = s[cc * C::CN + e];
         const u32x4 bop = pack_chunk<T>(pv);
 #pragma unroll
-        for (int dt = 0; dt < 2; ++dt) mma_chunk<T>(o[dt], load_t_chunk<T>(Vs, cc, lane, dt), bop);
+        for (int dt = 0; dt < 2; ++dt) mma_chunk<T>(o[dt], load_t_chunk<T>(Vs, 0, cc, lane, dt), bop);
       }
     }
     if (r0 + ql < rows) {
@@ -290,7 +224,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void tattn_any_bwd_ker
           for (int e = 0; e < C::CN; ++e) v[e] = s[cc * C::CN + e];
           const u32x4 bop = pack_chunk<T>(v);
 #pragma unroll
-          for (int dt = 0; dt < 2; ++dt) mma_chunk<T>(dq[dt], load_t_chunk<T>(tA, cc, lane, dt), bop);
+          for (int dt = 0; dt < 2; ++dt) mma_chunk<T>(dq[dt], load_t_chunk<T>(tA, 0, cc, lane, dt), bop);
         }
       }
       if (live) store_row64<T>(dqkv + (r0 + ql) * ldq + h * HD, dq, lane);
@@ -328,7 +262,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void tattn_any_bwd_ker
 #pragma unroll
           for (int i = 0; i < C::NLD; ++i) {
             const int c = lane + 64 * i, row = c / C::CPR, ch = c - row * C::CPR;
-            *(u32x4*)(tB + l_off<T>(row, ch)) = dv4[i];
+            *(u32x4*)(tB + tile_off<T>(row, ch)) = dv4[i];
             float a[C::CN], c2[C::CN];
             unpack_chunk<T>(dv4[i], a);
             unpack_chunk<T>(ov4[i], c2);
@@ -347,8 +281,8 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void tattn_any_bwd_ker
         for (int r = 0; r < 16; ++r) s[r] = dp[r] = 0.f;
 #pragma unroll
         for (int ks = 0; ks < C::KS; ++ks) {
-          mma_chunk<T>(s, *(const u32x4*)(tA + l_off<T>(ql, 2 * ks + g)), kf[ks]);
-          mma_chunk<T>(dp, *(const u32x4*)(tB + l_off<T>(ql, 2 * ks + g)), vf[ks]);
+          mma_chunk<T>(s, *(const u32x4*)(tA + tile_off<T>(ql, 2 * ks + g)), kf[ks]);
+          mma_chunk<T>(dp, *(const u32x4*)(tB + tile_off<T>(ql, 2 * ks + g)), vf[ks]);
         }
 #pragma unroll
         for (int rq = 0; rq < 4; ++rq) {
@@ -374,8 +308,8 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void tattn_any_bwd_ker
           const u32x4 pb = pack_chunk<T>(pv), sb = pack_chunk<T>(sv);
 #pragma unroll
           for (int dt = 0; dt < 2; ++dt) {
-            mma_chunk<T>(dv[dt], load_t_chunk<T>(tB, cc, lane, dt), pb);
-            mma_chunk<T>(dk[dt], load_t_chunk<T>(tA, cc, lane, dt), sb);
+            mma_chunk<T>(dv[dt], load_t_chunk<T>(tB, 0, cc, lane, dt), pb);
+            mma_chunk<T>(dk[dt], load_t_chunk<T>(tA, 0, cc, lane, dt), sb);
           }
         }
       }
@@ -385,10 +319,6 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void tattn_any_bwd_ker
       }
     }
   }
-}
-
-template <typename K> void set_lds_once(DeviceOnce& once, K* kern, size_t lds) {
-  once.run([&] { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); });
 }
 
 int64_t tattn_grid(int64_t units) {

@@ -341,6 +341,11 @@ struct DeviceOnce {
     }
   }
 };
+// raise kernel `kern`'s dynamic LDS limit to `lds` bytes, once per device.  `once` belongs to this kernel alone (a second kernel passed
+// with the same `once` would find the device's bit set and be skipped)
+template <typename K> void set_lds_once(DeviceOnce& once, K* kern, size_t lds) {
+  once.run([&] { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); });
+}
 #define ALPRO_CHECK(cond, ...)            \
   do {                                    \
     if (!(cond)) {                        \
