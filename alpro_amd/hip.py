@@ -731,6 +731,7 @@ def vit_final_pool(x, gamma, beta, eps, B, T, N, dtype):
 
 
 def bert_embed(ids, word, pos, type_emb, gamma, beta, eps, dtype, stats=False, drop_p=0.0, drop_seed=0):
+    """-> (y32, y in dtype) [, mean, rstd of the pre-LayerNorm rows with stats=True]."""
     lib = load()
     _dev(ids, torch.int64)
     B, L = ids.shape
@@ -743,6 +744,8 @@ def bert_embed(ids, word, pos, type_emb, gamma, beta, eps, dtype, stats=False, d
     _check(lib.alpro_bert_embed_fwd(_ptr(ids), _ptr(_dev(word, torch.float32)), _ptr(_dev(pos, torch.float32)), _ptr(_dev(type_emb, torch.float32)),
                                     _ptr(gamma), _ptr(beta), eps, _ptr(y32), _ptr(y_t), _CODE[dtype], _ptr(mean), _ptr(rstd), rows, L, D,
                                     drop_p, drop_seed, _stream()), "alpro_bert_embed_fwd")
+    if stats:
+        return y32, (y_t if y_t is not None else y32), mean, rstd
     return y32, (y_t if y_t is not None else y32)
 
 
