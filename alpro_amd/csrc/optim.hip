@@ -127,6 +127,140 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float
   }
 }
 
+// ---- parameter groups: adamw_kernel with the hyper-parameters of a chunk taken from a segment table (alpro_adamw_step_groups) ---------------
+// The table sits in the kernel arguments and is only read.  A wave's 64 chunks are 256 consecutive elements, so all but the few waves that
+// straddle a segment boundary (at most count - 1 per trip) need ONE segment per chunk.  The loop runs on the WAVE's base index (uniform
+// control flow): per chunk in flight the wave keeps the range and the hyper-parameters of the segment it met last in scalar registers, a
+// chunk inside that range costs two scalar compares and the update reads its hyper-parameters from SGPRs exactly as adamw_kernel reads its
+// arguments.  A wave that leaves the range walks the table again -- its chunks ascend, so at most `count` times, the powf pair of the
+// loss-scaling step size with it.  Straddling waves and the last, partial trip go one chunk at a time with a per-lane look-up.
+struct SegHP {
+  float lr, beta1, beta2, eps, weight_decay, step_size;
+};
+
+struct SegCache {   // wave-uniform: [lo, hi) of the cached segment (empty = nothing cached) and its hyper-parameters
+  int64_t lo = 0, hi = 0;
+  SegHP hp;
+};
+
+__device__ __forceinline__ int64_t first_lane_i64(int64_t x) {
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)(uint64_t)x), hi = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)x >> 32));
+  return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+// dyn_t > 0: dynamic loss scaling, the step size comes from the DEVICE step counter (dyn_t = applied steps + 1) and this segment's own lr / betas
+__device__ __forceinline__ SegHP seg_hp(const alpro_adamw_segment_t& s, float dyn_t) {
+  SegHP h = {s.lr, s.beta1, s.beta2, s.eps, s.weight_decay, s.step_size};
+  if (dyn_t > 0.f) h.step_size = s.correct_bias ? s.lr * sqrtf(1.0f - powf(s.beta2, dyn_t)) / (1.0f - powf(s.beta1, dyn_t)) : s.lr;
+  return h;
+}
+
+// qw: wave-uniform first element of a wave's 256.  True: all of [qw, qw + 256) lies in the segment c describes (found again if need be).
+__device__ __forceinline__ bool seg_find(const alpro_adamw_segments_t& tab, int64_t qw, float dyn_t, SegCache& c) {
+  if (qw >= c.lo && qw + 256 <= c.hi) return true;
+  int s = 0;
+  while (s < tab.count - 1 && qw >= tab.seg[s].end) ++s;
+  const bool last = s == tab.count - 1;
+  if (!last && qw + 256 > tab.seg[s].end) return false;   // a boundary inside the wave's 256 elements
+  c.lo = s ? tab.seg[s - 1].end : 0;
+  c.hi = last ? INT64_MAX : tab.seg[s].end;               // (the last end is n, which the wave's span may pass: its chunks do not)
+  c.hp = seg_hp(tab.seg[s], dyn_t);
+  c.hp.step_size = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(c.hp.step_size)));   // computed on the vector ALU, equal in every lane
+  return true;
+}
+
+// Per lane: the segment of the chunk that starts at q (a multiple of 4; so is every end but the last: a chunk has one segment).
+__device__ __forceinline__ SegHP seg_of_lane(const alpro_adamw_segments_t& tab, int64_t q, float dyn_t) {
+  int s = 0;
+  for (int k = 0; k < tab.count - 1; ++k) s += (q >= tab.seg[k].end) ? 1 : 0;
+  return seg_hp(tab.seg[s], dyn_t);
+}
+
+template <typename LP>
+__global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                                           int64_t n, const alpro_adamw_segments_t tab, const float* __restrict__ gnorm_sq,
+                                                           float max_norm, float grad_scale, const float* __restrict__ dyn, int grads_scaled,
+                                                           int zero_grad, LP* __restrict__ lp) {
+  float coef = grad_scale;
+  float dyn_t = 0.f;
+  if (dyn) {   // as adamw_kernel: a non-finite norm skips EVERY segment, the gradients are still consumed when the caller asked for that
+    if (!isfinite(*gnorm_sq)) {
+      if (zero_grad) {
+        const int64_t stride0 = (int64_t)gridDim.x * blockDim.x * 4;
+        for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += stride0)
+          for (int k = 0; k < 4 && i + k < n; ++k) g[i + k] = 0.f;
+      }
+      return;
+    }
+    if (grads_scaled) coef /= dyn[0];
+    dyn_t = dyn[2] + 1.0f;
+  }
+  if (gnorm_sq && max_norm > 0.f) {   // ONE coefficient from the global norm: clip_grad_norm_ is over all parameters, not per group
+    const float total = sqrtf(*gnorm_sq) * coef;
+    coef *= fminf(max_norm / (total + 1e-6f), 1.0f);
+  }
+  auto update = [&](const SegHP& h, float (&pv)[4], const float (&gv)[4], float (&mv)[4], float (&vv)[4]) {
+    const float lr = h.lr, beta1 = h.beta1, beta2 = h.beta2, eps = h.eps, weight_decay = h.weight_decay, step_size = h.step_size;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {   // the statements of adamw_kernel, unchanged: equal hyper-parameters give equal bits
+      const float gr = gv[k] * coef;
+      mv[k] = mv[k] * beta1 + (1.0f - beta1) * gr;
+      vv[k] = vv[k] * beta2 + (1.0f - beta2) * gr * gr;
+      const float denom = sqrtf(vv[k]) + eps;
+      pv[k] = pv[k] - step_size * (mv[k] / denom);
+      if (weight_decay > 0.f) pv[k] = pv[k] - lr * weight_decay * pv[k];
+    }
+  };
+  auto store4 = [&](int64_t i, const float (&pv)[4], const float (&mv)[4], const float (&vv)[4]) {
+    *(float4*)(p + i) = make_float4(pv[0], pv[1], pv[2], pv[3]);
+    *(float4*)(m + i) = make_float4(mv[0], mv[1], mv[2], mv[3]);
+    *(float4*)(v + i) = make_float4(vv[0], vv[1], vv[2], vv[3]);
+    if (zero_grad) *(float4*)(g + i) = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (sizeof(LP) == 2) {
+      if (lp) *(u32x2*)(lp + i) = mk2(pack2(pv[0], pv[1], (LP*)0), pack2(pv[2], pv[3], (LP*)0));   // the same roundings as alpro_cast_from_f32
+    }
+  };
+  auto one_chunk = [&](int64_t q) {   // a chunk on its own, element by element where it is ragged, its segment looked up by the lane
+    if (q >= n) return;
+    const int cnt = (q + 4 <= n) ? 4 : (int)(n - q);
+    const SegHP h = seg_of_lane(tab, q, dyn_t);
+    float pv[4] = {0.f, 0.f, 0.f, 0.f}, gv[4] = {0.f, 0.f, 0.f, 0.f}, mv[4] = {0.f, 0.f, 0.f, 0.f}, vv[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int k = 0; k < cnt; ++k) { pv[k] = p[q + k]; gv[k] = g[q + k]; mv[k] = m[q + k]; vv[k] = v[q + k]; }
+    update(h, pv, gv, mv, vv);
+    if (cnt == 4) {
+      store4(q, pv, mv, vv);
+    } else {
+      for (int k = 0; k < cnt; ++k) {
+        p[q + k] = pv[k]; m[q + k] = mv[k]; v[q + k] = vv[k];
+        if (zero_grad) g[q + k] = 0.f;
+        if constexpr (sizeof(LP) == 2) { if (lp) lp[q + k] = from_f32<LP>(pv[k]); }
+      }
+    }
+  };
+  SegCache c0, c1;   // one per chunk in flight: the two are `stride` elements apart and usually in different segments
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x * 4;
+  const int lane4 = (int)(threadIdx.x & 63) * 4;
+  // the chunks of adamw_kernel's walk, thread for thread: i = ((blockIdx.x * blockDim.x + threadIdx.x) * 4 + trips * 2 * stride, j = i + stride
+  for (int64_t iw = first_lane_i64(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4); iw < n; iw += 2 * stride) {
+    const int64_t jw = iw + stride, i = iw + lane4, j = jw + lane4;
+    if (jw + 256 <= n && seg_find(tab, iw, dyn_t, c0) && seg_find(tab, jw, dyn_t, c1)) {
+      // two float4 of each array in flight as in adamw_kernel; every lane's two chunks are whole and each in ONE segment
+      const float4 a0 = *(const float4*)(p + i), b0 = *(const float4*)(g + i), m0 = *(const float4*)(m + i), d0 = *(const float4*)(v + i);
+      const float4 a1 = *(const float4*)(p + j), b1 = *(const float4*)(g + j), m1 = *(const float4*)(m + j), d1 = *(const float4*)(v + j);
+      float pv0[4] = {a0.x, a0.y, a0.z, a0.w}, mv0[4] = {m0.x, m0.y, m0.z, m0.w}, vv0[4] = {d0.x, d0.y, d0.z, d0.w};
+      float pv1[4] = {a1.x, a1.y, a1.z, a1.w}, mv1[4] = {m1.x, m1.y, m1.z, m1.w}, vv1[4] = {d1.x, d1.y, d1.z, d1.w};
+      const float gv0[4] = {b0.x, b0.y, b0.z, b0.w}, gv1[4] = {b1.x, b1.y, b1.z, b1.w};
+      update(c0.hp, pv0, gv0, mv0, vv0);
+      store4(i, pv0, mv0, vv0);
+      update(c1.hp, pv1, gv1, mv1, vv1);
+      store4(j, pv1, mv1, vv1);
+      continue;
+    }
+    one_chunk(i);
+    one_chunk(j);
+  }
+}
+
 // One thread: the loss-scale schedule of apex's dynamic LossScaler (scale_window 2000, halve on overflow, double after a window of
 // clean steps, clamped), entirely on the device -- no host sync in the training loop.
 __global__ void loss_scale_update_kernel(float* __restrict__ dyn, const float* __restrict__ gnorm_sq, float growth, float backoff,
@@ -187,6 +321,43 @@ extern "C" int alpro_adamw_step_lp(float* p, float* g, float* m, float* v, int64
   else ALPRO_ADAMW_GO(float, (float*)nullptr);
 #undef ALPRO_ADAMW_GO
   return check_launch("alpro_adamw_step");
+}
+
+#define ALPRO_STR_(x) #x
+#define ALPRO_STR(x) ALPRO_STR_(x)
+
+extern "C" int alpro_adamw_step_groups(float* p, float* g, float* m, float* v, int64_t n, const alpro_adamw_segments_t* segments,
+                                       const float* gnorm_sq, float max_norm, float grad_scale, const float* dyn_state, int grads_scaled,
+                                       int zero_grad, void* lp, int lp_dtype, void* stream) {
+  ALPRO_CHECK(p && g && m && v && n > 0 && segments, "alpro_adamw_step_groups: bad args");
+  ALPRO_CHECK(segments->count <= ALPRO_ADAMW_MAX_SEGMENTS,
+              "alpro_adamw_step_groups: more than ALPRO_ADAMW_MAX_SEGMENTS = " ALPRO_STR(ALPRO_ADAMW_MAX_SEGMENTS) " segments (the table travels in the kernel arguments)");
+  ALPRO_CHECK(segments->count >= 1, "alpro_adamw_step_groups: an empty segment table");
+  ALPRO_CHECK(!dyn_state || gnorm_sq, "alpro_adamw_step_groups: dynamic loss scaling needs the squared gradient norm (overflow detection)");
+  ALPRO_CHECK(((uintptr_t)p % 16) == 0 && ((uintptr_t)g % 16) == 0 && ((uintptr_t)m % 16) == 0 && ((uintptr_t)v % 16) == 0,
+              "alpro_adamw_step_groups: buffers must be 16-byte aligned");
+  ALPRO_CHECK(!lp || ((lp_dtype == ALPRO_BF16 || lp_dtype == ALPRO_F16) && ((uintptr_t)lp % 8) == 0), "alpro_adamw_step_groups: the mirror is a 16-bit, 8-byte-aligned buffer");
+  alpro_adamw_segments_t tab = {};   // (a copy with the unused tail cleared: the kernel arguments carry no caller garbage)
+  tab.count = segments->count;
+  int64_t prev = 0;
+  for (int k = 0; k < segments->count; ++k) {
+    const alpro_adamw_segment_t& s = segments->seg[k];
+    ALPRO_CHECK(s.end > prev && (s.end % 4 == 0 || k == segments->count - 1),
+                "alpro_adamw_step_groups: segment ends must ascend strictly and, but for the last, be multiples of 4");
+    prev = s.end;
+    tab.seg[k] = s;
+  }
+  ALPRO_CHECK(prev == n, "alpro_adamw_step_groups: the segments must cover [0, n) exactly");
+  const dim3 grid(grid_for(n)), blk(256);
+  hipStream_t st = (hipStream_t)stream;
+#define ALPRO_ADAMW_GROUPS_GO(LP_, ptr)                                                                                                  \
+  hipLaunchKernelGGL(adamw_groups_kernel<LP_>, grid, blk, 0, st, p, g, m, v, n, tab, gnorm_sq, max_norm, grad_scale, dyn_state, grads_scaled, \
+                     zero_grad, ptr)
+  if (lp && lp_dtype == ALPRO_BF16) ALPRO_ADAMW_GROUPS_GO(bf16_t, (bf16_t*)lp);
+  else if (lp) ALPRO_ADAMW_GROUPS_GO(f16_t, (f16_t*)lp);
+  else ALPRO_ADAMW_GROUPS_GO(float, (float*)nullptr);
+#undef ALPRO_ADAMW_GROUPS_GO
+  return check_launch("alpro_adamw_step_groups");
 }
 
 extern "C" int alpro_adamw_step(float* p, float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,

@@ -26,7 +26,7 @@ EXPORTS = ["alpro_hip_last_error", "alpro_hip_abi_version", "alpro_hip_set_optio
            "alpro_vit_final_pool", "alpro_bert_embed_fwd", "alpro_cast_from_f32", "alpro_attn_bwd", "alpro_attn_temporal_bwd",
            "alpro_layernorm_bwd", "alpro_transpose", "alpro_transpose_batch", "alpro_gelu_bwd", "alpro_cls_mean_bwd", "alpro_scatter_add_rows", "alpro_gather_cast", "alpro_sumsq", "alpro_adamw_step", "alpro_gemm_tn_acc", "alpro_gemm_tn_acc_ws", "alpro_gemm_tn_workspace_bytes", "alpro_gemm_tn_ranges", "alpro_colsum_acc", "alpro_softmax_xent", "alpro_vtc_loss_fwd", "alpro_vtc_loss_bwd", "alpro_prepare_clips", "alpro_loss_scale_update", "alpro_add_layernorm_fwd", "alpro_layernorm_bwd_emit", "alpro_gemm_batch", "alpro_tproj_small", "alpro_attn_cls_fwd", "alpro_gemm_rows_f32", "alpro_gather_seq_fwd", "alpro_gather_seq_bwd", "alpro_scatter_add_rows_ordered",
            "alpro_hip_sched_workspace_bytes", "alpro_hip_set_sched_workspace", "alpro_hip_release_stream", "alpro_gemm_qkv_tattn", "alpro_add_layernorm_pre_mlp2", "alpro_adamw_step_lp",
-           "alpro_gemm_rows_f32_relu_mask", "alpro_clip_pool"]
+           "alpro_gemm_rows_f32_relu_mask", "alpro_clip_pool", "alpro_adamw_step_groups"]
 
 
 class GemmDesc(ctypes.Structure):
@@ -52,6 +52,18 @@ class TprojJob(ctypes.Structure):
 class TransposeJob(ctypes.Structure):
     _fields_ = [("in_", ctypes.c_void_p), ("out", ctypes.c_void_p), ("ld_in", ctypes.c_int64), ("ld_out", ctypes.c_int64),
                 ("R", ctypes.c_int32), ("C", ctypes.c_int32), ("Rpad", ctypes.c_int32), ("tile0", ctypes.c_int32)]   # 48 bytes
+
+
+ADAMW_MAX_SEGMENTS = 32   # ALPRO_ADAMW_MAX_SEGMENTS
+
+
+class AdamWSegment(ctypes.Structure):
+    _fields_ = [("end", ctypes.c_int64), ("lr", ctypes.c_float), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float), ("eps", ctypes.c_float),
+                ("weight_decay", ctypes.c_float), ("step_size", ctypes.c_float), ("correct_bias", ctypes.c_int32), ("reserved0", ctypes.c_int32)]   # 40 bytes
+
+
+class AdamWSegments(ctypes.Structure):
+    _fields_ = [("count", ctypes.c_int32), ("reserved0", ctypes.c_int32), ("seg", AdamWSegment * ADAMW_MAX_SEGMENTS)]
 
 
 ABI_VERSION = 22
@@ -102,6 +114,7 @@ def load():
     lib.alpro_transpose_batch.argtypes = [vp, i32, i32, i32, vp]
     lib.alpro_adamw_step.argtypes = [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, vp, f32, f32, vp, i32, i32, i32, vp]
     lib.alpro_adamw_step_lp.argtypes = [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, vp, f32, f32, vp, i32, i32, i32, vp, i32, vp]
+    lib.alpro_adamw_step_groups.argtypes = [vp, vp, vp, vp, i64, ctypes.POINTER(AdamWSegments), vp, f32, f32, vp, i32, i32, vp, i32, vp]
     lib.alpro_loss_scale_update.argtypes = [vp, vp, f32, f32, i32, f32, f32, vp]
     lib.alpro_gather_cast.argtypes = [vp, i64, vp, i32, i32, i32, i32, i32, i32, vp, i32, f32, f32, u32, vp, vp, vp, ctypes.c_size_t, vp]
     lib.alpro_cls_mean_bwd.argtypes = [vp, i64, vp, i32, i32, i32, vp]
@@ -788,6 +801,32 @@ def adamw_step(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step_size, gnorm
                                    _ptr(gnorm_sq), max_norm, grad_scale, _ptr(dyn_state), int(bool(grads_scaled)), int(bool(correct_bias)), int(bool(zero_grad)),
                                    _ptr(lp), _CODE[lp.dtype] if lp is not None else 0, _stream()),
            "alpro_adamw_step")
+
+
+def adamw_step_groups(p, g, m, v, segments, gnorm_sq=None, max_norm=0.0, grad_scale=1.0, dyn_state=None, grads_scaled=True, zero_grad=False, lp=None):
+    """adamw_step with per-segment hyper-parameters (alpro_adamw_step_groups): `segments` is a sequence of dicts {end, lr, beta1, beta2, eps,
+    weight_decay, step_size, correct_bias}, contiguous and ascending over [0, p.numel()), every end but the last a multiple of 4.  The table
+    is handed over by value with the launch -- no device buffer, no copy, no sync; more than ADAMW_MAX_SEGMENTS entries are refused by the
+    library.  Everything else as adamw_step."""
+    lib = load()
+    for t in (p, g, m, v):
+        _dev(t, torch.float32)
+    if dyn_state is not None:
+        _dev(dyn_state, torch.float32)
+        assert dyn_state.numel() >= 4 and gnorm_sq is not None
+    if lp is not None:
+        _dev(lp)
+        if lp.dtype not in (torch.float16, torch.bfloat16) or lp.numel() != p.numel() or not lp.is_contiguous():
+            raise RuntimeError("adamw_step_groups: lp must be a contiguous 16-bit tensor with p's number of elements")
+    tab = AdamWSegments()
+    tab.count = len(segments)     # (a table over the bound goes to the library as it is counted: the refusal names the bound)
+    for dst, s in zip(tab.seg, segments):
+        dst.end, dst.lr, dst.beta1, dst.beta2, dst.eps = int(s["end"]), s["lr"], s["beta1"], s["beta2"], s["eps"]
+        dst.weight_decay, dst.step_size, dst.correct_bias = s["weight_decay"], s["step_size"], int(bool(s["correct_bias"]))
+    _check(lib.alpro_adamw_step_groups(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), ctypes.byref(tab), _ptr(gnorm_sq), max_norm, grad_scale,
+                                       _ptr(dyn_state), int(bool(grads_scaled)), int(bool(zero_grad)), _ptr(lp), _CODE[lp.dtype] if lp is not None else 0,
+                                       _stream()),
+           "alpro_adamw_step_groups")
 
 
 def loss_scale_update(dyn_state, gnorm_sq, growth=2.0, backoff=0.5, window=2000, min_scale=1.0, max_scale=2.0 ** 24):

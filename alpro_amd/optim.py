@@ -9,7 +9,9 @@ FOUR flat fp32 buffers (0.94 GB each for AlproForPretrain's 234 M trained parame
   * the gradient all-reduce is a handful of large RCCL calls over that buffer (no bucketing copies),
   * grad-norm + clip + AdamW are two kernels (alpro_sumsq, alpro_adamw_step), zero_grad is one memset.
 
-Same constructor / param_groups surface as the reference's AdamW so a driver only swaps the class.  Parameters that never
+Same constructor / param_groups surface as the reference's AdamW so a driver only swaps the class -- a parameter list or the usual list
+of group dicts with their own lr / betas / eps / weight_decay / correct_bias (build_param_groups makes the common ones); with several groups the
+step is still one pass, the hyper-parameters travel as a segment table in the kernel arguments (alpro_adamw_step_groups).  Parameters that never
 receive a gradient (the frozen prompter, the unused Kinetics head) are left out instead of being zero-filled and reduced.
 """
 import math
@@ -73,11 +75,71 @@ class _FlatView:
         self.grad = grad
 
 
+NO_DECAY = ("bias", "LayerNorm.weight", "norm", "embeddings")
+
+
+def build_param_groups(model, lr, weight_decay, no_decay=NO_DECAY, lr_mult=None):
+    """The usual fine-tuning groups for FlatAdamW (or any torch optimizer): [{'params', 'lr', 'weight_decay', 'lr_mult'}, ...].
+
+    model: an nn.Module, or an iterable of (name, parameter) pairs.  A parameter gets weight_decay 0 when one of the `no_decay` strings occurs
+    in its name (biases, LayerNorm / norm weights, the embedding tables) or when a submodule names it in its own no_weight_decay() (the ViT's
+    pos_embed / cls_token / time_embed), `weight_decay` otherwise.  lr_mult: {name prefix: multiplier}, e.g. {"visual_encoder.": 0.1,
+    "text_encoder.": 0.1} for a smaller learning rate on the pretrained encoders; the longest matching prefix counts, no match is 1.0.
+    Each group carries lr = lr * multiplier and the multiplier itself, so a driver's schedule is
+    `for pg in optimizer.param_groups: pg['lr'] = lr_this_step * pg.get('lr_mult', 1.0)`.  Groups appear in the order their first parameter
+    does; parameters that do not require grad are left out; a parameter reachable under two names (tied weights) counts once."""
+    skip = set()
+    if isinstance(model, torch.nn.Module):
+        named = list(model.named_parameters())
+        for prefix, mod in model.named_modules():
+            fn = getattr(mod, "no_weight_decay", None)
+            if callable(fn):
+                skip.update((prefix + "." if prefix else "") + n for n in fn())
+    else:
+        named = list(model)
+    lr_mult = dict(lr_mult or {})
+    groups, seen = {}, set()
+    for name, p in named:
+        if not p.requires_grad or id(p) in seen:
+            continue
+        seen.add(id(p))
+        decays = not (name in skip or any(nd in name for nd in no_decay))
+        hits = [k for k in lr_mult if name.startswith(k)]
+        mult = float(lr_mult[max(hits, key=len)]) if hits else 1.0
+        key = (decays, mult)
+        if key not in groups:
+            groups[key] = dict(params=[], lr=lr * mult, weight_decay=weight_decay if decays else 0.0, lr_mult=mult)
+        groups[key]["params"].append(p)
+    return list(groups.values())
+
+
 class FlatAdamW:
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, correct_bias=True, max_grad_norm=None,
                  allreduce=True, bucket_elems=64 << 20, overlap_backward=None, wire_dtype=None, fused_zero_grad=True):
-        self.params = [p for p in params if p.requires_grad]
-        self.param_groups = [dict(params=self.params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, correct_bias=correct_bias)]
+        # `params`: an iterable of parameters (ONE group, the reference drivers' case) or of group dicts as torch.optim takes them --
+        # {'params': [...], and any of lr / betas / eps / weight_decay / correct_bias}, the rest from the keyword defaults.  Extra keys
+        # (build_param_groups' 'lr_mult') are kept.  Parameters that do not require grad are dropped from their group.
+        params = list(params)
+        if not params:
+            raise ValueError("FlatAdamW: got an empty parameter list")
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, correct_bias=correct_bias)
+        if isinstance(params[0], dict):
+            if not all(isinstance(g, dict) and "params" in g for g in params):
+                raise ValueError("FlatAdamW: parameter groups are dicts with a 'params' entry; do not mix them with bare parameters")
+            groups = [dict(defaults, **dict(g, params=[g["params"]] if torch.is_tensor(g["params"]) else list(g["params"]))) for g in params]
+        else:
+            groups = [dict(defaults, params=params)]
+        seen = set()
+        for g in groups:
+            if any(not torch.is_tensor(p) for p in g["params"]):
+                raise TypeError("FlatAdamW: a group's 'params' holds something that is not a tensor")
+            if any(id(p) in seen for p in g["params"]):
+                raise ValueError("FlatAdamW: some parameters appear in more than one parameter group")
+            seen.update(id(p) for p in g["params"])
+            g["params"] = [p for p in g["params"] if p.requires_grad]
+            g["betas"] = tuple(g["betas"])
+        self.param_groups = groups
+        self.params = groups[0]["params"] if len(groups) == 1 else [p for g in groups for p in g["params"]]   # constructor order
         self.max_grad_norm = max_grad_norm
         self.allreduce = allreduce
         self.bucket_elems = bucket_elems
@@ -139,7 +201,13 @@ class FlatAdamW:
             return False
         # matrices first (original order), vectors after: BERT's query/key/value weights (and their biases) then sit back
         # to back in the flat gradient buffer, so the fused-QKV weight gradient is ONE N=2304 GEMM into a (2304, 768) view
-        live.sort(key=lambda p: p.dim() < 2)
+        if len(self.param_groups) == 1:
+            live.sort(key=lambda p: p.dim() < 2)
+        else:
+            # several groups: (group, matrices before vectors, original order) -- a group is at most two runs of the flat buffers, and the
+            # q / k / v weights of one layer stay neighbours whenever they share a group (train.fused_grad_view falls back when they do not)
+            gi = self._group_index()
+            live.sort(key=lambda p: (gi[id(p)], p.dim() < 2))
         dev = live[0].device
         offs, n = [], 0
         for p in live:
@@ -169,6 +237,38 @@ class FlatAdamW:
             pend, self._pending_state = self._pending_state, None
             self._restore_moments(pend)
         return True
+
+    def _group_index(self):
+        return {id(p): k for k, g in enumerate(self.param_groups) for p in g["params"]}
+
+    def add_param_group(self, group):
+        if self.flat is not None:
+            raise RuntimeError("FlatAdamW.add_param_group: the flat buffers are built (a step() has run); the layout cannot take another "
+                               "group -- pass every group to the constructor")
+        raise NotImplementedError("FlatAdamW.add_param_group: pass every group to the constructor")
+
+    def _segments(self, step):
+        """The segment table of alpro_adamw_step_groups for optimizer step `step`: per group its runs of the flat buffers (matrices, vectors;
+        neighbouring runs of one group are one segment), each with the group's hyper-parameters as they stand NOW and the host step size."""
+        f = self.flat
+        gi = self._group_index()
+        runs = []   # [group index, end]
+        for p, o in zip(f["live"], f["offs"]):
+            k, end = gi[id(p)], o + (p.numel() + 3) // 4 * 4
+            if runs and runs[-1][0] == k:
+                runs[-1][1] = end
+            else:
+                runs.append([k, end])
+        segs = []
+        for k, end in runs:
+            grp = self.param_groups[k]
+            lr, (b1, b2) = grp["lr"], grp["betas"]
+            step_size = lr
+            if grp["correct_bias"]:
+                step_size = lr * math.sqrt(1.0 - b2 ** step) / (1.0 - b1 ** step)
+            segs.append(dict(end=end, lr=lr, beta1=b1, beta2=b2, eps=grp["eps"], weight_decay=grp["weight_decay"], step_size=step_size,
+                             correct_bias=grp["correct_bias"]))
+        return segs
 
     def _mark_dirty(self, _p=None):
         self._g_clean = False
@@ -440,6 +540,7 @@ class FlatAdamW:
         step_size = lr
         if grp["correct_bias"]:
             step_size = lr * math.sqrt(1.0 - b2 ** self.step_count) / (1.0 - b1 ** self.step_count)
+        grouped = len(self.param_groups) > 1   # else: the one-group call, exactly as before parameter groups existed
         norm = None
         sc = self.scaler
         if sc is not None:
@@ -458,9 +559,13 @@ class FlatAdamW:
                 f["lp"] = torch.empty(f["n"], dtype=dt, device=f["p"].device)
                 hip.cast(f["p"], dt, out=f["lp"])
             lp = f["lp"]
-        hip.adamw_step(f["p"], f["g"], f["m"], f["v"], lr, b1, b2, grp["eps"], grp["weight_decay"], step_size, norm,
-                       float(self.max_grad_norm or 0.0), 1.0 / world, dyn_state=sc.state if sc is not None else None,
-                       grads_scaled=self._grads_scaled, correct_bias=grp["correct_bias"], zero_grad=self.fused_zero_grad, lp=lp)
+        if grouped:   # still ONE pass and one launch: the hyper-parameters travel as a segment table in the kernel arguments
+            hip.adamw_step_groups(f["p"], f["g"], f["m"], f["v"], self._segments(self.step_count), norm, float(self.max_grad_norm or 0.0), 1.0 / world,
+                                  dyn_state=sc.state if sc is not None else None, grads_scaled=self._grads_scaled, zero_grad=self.fused_zero_grad, lp=lp)
+        else:
+            hip.adamw_step(f["p"], f["g"], f["m"], f["v"], lr, b1, b2, grp["eps"], grp["weight_decay"], step_size, norm,
+                           float(self.max_grad_norm or 0.0), 1.0 / world, dyn_state=sc.state if sc is not None else None,
+                           grads_scaled=self._grads_scaled, correct_bias=grp["correct_bias"], zero_grad=self.fused_zero_grad, lp=lp)
         self._g_clean = self.fused_zero_grad
         self._clean_epoch = _backward_epoch()
         if sc is not None:  # overflow -> the kernel skipped the update; the schedule halves / grows the scale on the device
@@ -478,6 +583,10 @@ class FlatAdamW:
         meaning (parameter index in the constructor's list, offset, numel).  Savers may move / narrow the tensors
         (E2E_TrainingRestorer stores fp16 on the CPU, load_save.py:181-196); load_state_dict widens them again."""
         groups = [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups]
+        if len(self.param_groups) > 1:   # which parameters (indices in constructor order) each group holds; one group: the format of old
+            pos = {id(p): i for i, p in enumerate(self.params)}
+            for saved, g in zip(groups, self.param_groups):
+                saved["params"] = [pos[id(p)] for p in g["params"]]
         # under loss scaling the bias correction runs on the scaler's DEVICE counter of APPLIED steps (overflow-skipped steps do not count,
         # the host `step` does): the scaler state travels with the optimizer so that a resumed run continues bit for bit (ADVICE r3)
         extra = dict(loss_scaler=self.scaler.state_dict()) if self.scaler is not None else {}
@@ -490,7 +599,20 @@ class FlatAdamW:
     def load_state_dict(self, sd):
         """Restore the step counter, hyper-parameters and moments written by state_dict().  The flat buffers only exist after the
         first backward + step(): before that the moments are parked and applied by the first step(), which checks that the same set
-        of parameters is being trained (the layout is a pure function of which parameters receive gradients)."""
+        of parameters is being trained (the layout is a pure function of which parameters receive gradients).  With several groups the
+        checkpoint says which parameters (indices in constructor order) each group held: a different grouping is refused before anything
+        is restored.  A checkpoint of one group without indices (the format from before parameter groups) loads into one group."""
+        saved_groups = list(sd.get("param_groups", []))
+        if saved_groups:
+            pos = {id(p): i for i, p in enumerate(self.params)}
+            mine = [[pos[id(p)] for p in g["params"]] for g in self.param_groups]
+            # a checkpoint of one group carries no indices (the format from before parameter groups): it holds every parameter
+            theirs = [[int(i) for i in g["params"]] if "params" in g else None for g in saved_groups]
+            if len(saved_groups) != len(self.param_groups) or any(t is not None and t != m for t, m in zip(theirs, mine)) or \
+                    (len(saved_groups) > 1 and any(t is None for t in theirs)):
+                raise ValueError("FlatAdamW.load_state_dict: the checkpoint's parameter grouping (%d groups of %s parameters) differs from this "
+                                 "optimizer's (%d groups of %s)" % (len(saved_groups), [len(t) if t is not None else "all" for t in theirs],
+                                                                   len(mine), [len(m) for m in mine]))
         self.step_count = int(sd["step"])
         self._scaler_steps_synced = None   # re-seed the device step counter from the restored host counter at the next step() ...
         if sd.get("loss_scaler") is not None:   # ... unless the checkpoint carries the scaler itself: then its applied-step count is authoritative
@@ -499,9 +621,10 @@ class FlatAdamW:
             if sc is not None:
                 sc.load_state_dict(sd["loss_scaler"])
                 self._scaler_steps_synced = sc
-        for g, saved in zip(self.param_groups, sd.get("param_groups", [])):
+        for g, saved in zip(self.param_groups, saved_groups):
             for k, v in saved.items():
-                g[k] = tuple(v) if k == "betas" else v
+                if k != "params":
+                    g[k] = tuple(v) if k == "betas" else v
         if sd.get("m") is None:
             self._pending_state = None
             if self.flat is not None:

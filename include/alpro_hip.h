@@ -478,6 +478,30 @@ int alpro_adamw_step_lp(float* p, float* g, float* m, float* v, int64_t n, float
                         float step_size, const float* gnorm_sq, float max_norm, float grad_scale, const float* dyn_state, int grads_scaled,
                         int correct_bias, int zero_grad, void* lp, int lp_dtype, void* stream);
 
+/* Parameter groups: the same pass with the hyper-parameters taken from a SEGMENT TABLE instead of scalars.  Segment k covers the elements
+ * [seg[k-1].end, seg[k].end) of the flat buffers (seg[-1].end = 0); the ends ascend strictly, the last one equals n and every other one is
+ * a multiple of 4 (a float4 never straddles two segments).  Every segment carries what the scalar entry points take once: lr, betas, eps, weight_decay, the
+ * caller's step_size (lr * sqrt(1-b2^t) / (1-b1^t), or lr) and correct_bias.  The table travels BY VALUE in the kernel arguments: a caller
+ * may rewrite it before every step without a device buffer, a copy or a host sync.  At most ALPRO_ADAMW_MAX_SEGMENTS segments (16 groups x
+ * {matrices, vectors}); a longer table is refused, never truncated. */
+#define ALPRO_ADAMW_MAX_SEGMENTS 32
+typedef struct alpro_adamw_segment_t {
+  int64_t end;                 /* one past the last element of the segment */
+  float lr, beta1, beta2, eps, weight_decay, step_size;
+  int32_t correct_bias, reserved0;
+} alpro_adamw_segment_t;       /* 40 bytes */
+typedef struct alpro_adamw_segments_t {
+  int32_t count, reserved0;
+  alpro_adamw_segment_t seg[ALPRO_ADAMW_MAX_SEGMENTS];
+} alpro_adamw_segments_t;
+/* Everything else as alpro_adamw_step_lp: ONE clip coefficient from the global *gnorm_sq, grad_scale, zero_grad, the 16-bit mirror; with
+ * dyn_state a non-finite norm skips EVERY segment (gradients still cleared when asked) and each segment's step size is recomputed from the
+ * device step counter with that segment's lr, betas and correct_bias.  Segments with equal hyper-parameters give bit for bit what one
+ * alpro_adamw_step_lp call over the whole buffer gives. */
+int alpro_adamw_step_groups(float* p, float* g, float* m, float* v, int64_t n, const alpro_adamw_segments_t* segments, const float* gnorm_sq,
+                            float max_norm, float grad_scale, const float* dyn_state, int grads_scaled, int zero_grad, void* lp, int lp_dtype,
+                            void* stream);
+
 /* After alpro_adamw_step on the same stream: *gnorm_sq not finite -> S = max(S * backoff, min_scale), tracker = 0, skipped += 1;
  * else applied += 1, tracker += 1 and after `window` clean steps S = min(S * growth, max_scale).  apex defaults: growth 2, backoff 0.5,
  * window 2000, initial S 2^16, max 2^24. */
