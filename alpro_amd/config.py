@@ -143,16 +143,6 @@ def _several_ranks():
         return False
 
 
-def _new_side_stream(device):
-    """A side stream; ALPRO_SIDE_PRIORITY = default | high | low picks its HIP priority (measurement switch: high costs 14 %, there is no class below normal -- profiles/r6_hw_queues.txt, section 4)."""
-    import torch
-    pr = os.environ.get("ALPRO_SIDE_PRIORITY", "default")
-    if pr == "default":
-        return torch.cuda.Stream(device)
-    lo, hi = torch.cuda.Stream.priority_range()   # (lowest, highest): numerically lower = higher priority
-    return torch.cuda.Stream(device, priority=hi if pr == "high" else lo)
-
-
 def set_wgrad_stream(v):
     _wgrad_stream[0] = bool(v)
 
@@ -171,15 +161,15 @@ def wgrad_side_stream(device):
         return None
     import torch
     cur = torch.cuda.current_stream(device)
-    if os.environ.get("ALPRO_WGRAD_STREAM_NESTED", "0") != "1" and any(s.cuda_stream == cur.cuda_stream for s in _TEXT_SIDE.values()):
+    if any(s.cuda_stream == cur.cuda_stream for s in _TEXT_SIDE.values()):
         # a backward that already runs on the text side stream keeps its weight gradients there: at most four streams are active at a time (launch, text,
         # weight gradients in backward; launch, text, 2 x prompter in forward) -- the number of hardware queues that do not share a dispatch pipe
-        # (profiles/r6_hw_queues.txt; nested form 148.75 ms, this one 148.5)
+        # (profiles/r6_hw_queues.txt: a side stream of the side stream measured 148.75 ms against 148.5; default stream priority: high costs 14 %)
         return None
     key = (device.index if device.index is not None else torch.cuda.current_device(), cur.cuda_stream)
     ent = _WGRAD_SIDE.get(key)
     if ent is None:
-        ent = _WGRAD_SIDE[key] = [_new_side_stream(device), False]
+        ent = _WGRAD_SIDE[key] = [torch.cuda.Stream(device), False]
     ent[1] = True
     return ent[0]
 
@@ -194,7 +184,7 @@ def side_streams_of_current(device):
     key = (device.index if device.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(device).cuda_stream)
     ent = _WGRAD_SIDE.get(key)
     if ent is None:
-        ent = _WGRAD_SIDE[key] = [_new_side_stream(device), False]
+        ent = _WGRAD_SIDE[key] = [torch.cuda.Stream(device), False]
     return [ent[0].cuda_stream]
 
 
@@ -236,7 +226,7 @@ def text_side_stream(device):
     key = (device.index if device.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(device).cuda_stream)
     s = _TEXT_SIDE.get(key)
     if s is None:
-        s = _TEXT_SIDE[key] = _new_side_stream(device)
+        s = _TEXT_SIDE[key] = torch.cuda.Stream(device)
     return s
 
 
@@ -279,7 +269,7 @@ def prompter_side_stream(device):
     key = (device.index if device.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(device).cuda_stream)
     s = _PROMPTER_SIDE.get(key)
     if s is None:
-        s = _PROMPTER_SIDE[key] = _new_side_stream(device)
+        s = _PROMPTER_SIDE[key] = torch.cuda.Stream(device)
     return s
 
 

@@ -137,12 +137,7 @@ __device__ __forceinline__ void pv_tiles(f32x16 (&o)[2], const f32x16 (&p)[NKT],
 // scheduler per key tile (its reads would pile up in VGPRs otherwise), so every key tile began with an exposed LDS round trip, and inside a
 // tile the reads were issued one step ahead: ~35 % of a query tile's cycles went to `s_waitcnt lgkmcnt` in front of an MFMA.  Step i =
 // (key tile i / (2 CPT), P chunk (i / 2) % CPT, d half i & 1); the ring holds PDV chunks; a scheduling fence per step keeps the order.
-#ifndef ATTN_PDV
-#define ATTN_PDV 3   // ring depths of the 7-tile (ViT) form; measurement builds override them
-#endif
-#ifndef ATTN_PDK
-#define ATTN_PDK 4
-#endif
+constexpr int PV_RING = 3, K_RING = 4;   // ring depths of the 7-tile (ViT) form
 template <typename T, int NKT, int PDV = 3>
 __device__ __forceinline__ void pv_tiles_pipelined(f32x16 (&o)[2], const f32x16 (&p)[NKT], const char* vt, int lane) {
   typedef TileCfg<T> C;
@@ -373,20 +368,12 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_kernel(const T* __restrict_
   };
   // query tiles of this wave: t, t + 4, ... with t rotated by the workgroup index, so that the wave with one tile less (7 tiles on 4 waves)
   // is not the same SIMD's in the two workgroups that share a CU
-#ifdef ATTN_NO_ROT
-  int seq = wave;
-#else
   int seq = (wave + (int)(blockIdx.x >> 3)) & 3;
-#endif
   // The tile that carries the CLS parts costs its wave ~2000 more VALU instructions (part splits, DPP joins over all NKT * 16 score registers,
   // twice).  With 7 tiles on 4 waves the walk above gives it -- the last tile -- to a wave that has two tiles, i.e. puts the extras on the
   // workgroup's critical path; swapped with the one tile of the wave that has a round less (positions 3 <-> 6 at L = 197) they ride for free.
   int swap_a = -1, swap_b = -1;
-#ifdef ATTN_NO_CLS_SWAP   // (measurement builds, tools/build_attn_variants.sh)
-  if (false) {
-#else
   if (CLS && cls_tile >= 0 && cls_tile == ntile - 1 && (ntile & 3) != 0 && (cls_tile & 3) != 3 && ntile > 4) {
-#endif
     swap_a = cls_tile;
     swap_b = ((ntile - 1) & ~3) - 1;   // the last position of the walk that starts at 3: the wave with one tile less
   }
@@ -402,11 +389,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_kernel(const T* __restrict_
     const T* src = base + (int64_t)row * ldq;
     dma16(row < L ? (const char*)(src + 2 * H * HD + ((slot ^ (((row >> 1) & 1) << 2)) << 3)) : zero, __builtin_amdgcn_readfirstlane(v_lds + piece * 1024));
   }
-#ifdef ATTN_NO_KV_SPLIT
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#else
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NKT) : "memory");   // K and Q have landed (in-order return); the NKT V pieces may still be in flight
-#endif
   __syncthreads();
 
   const float sl = scale * LOG2E;
@@ -423,7 +406,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_kernel(const T* __restrict_
     // accumulators).  The compiler's own order kept two reads in flight and waited for one in front of every MFMA.  ViT shape -3 % on one box
     // (profiles/r6_attn_fwd_rings.txt); with 8 key tiles the 128 score registers leave no room for the ring (spills, +2..4 %): compiler order.
     if constexpr (NKT <= 7) {
-      constexpr int NF = NKT * 4, PDK = ATTN_PDK;
+      constexpr int NF = NKT * 4, PDK = K_RING;
       auto kfrag = [&](int i) __attribute__((always_inline)) {
         const int ks = i / NKT, krow = (i % NKT) * 32 + ql;
         return *(const u32x4*)(Ks + krow * RB + (((2 * ks + g) ^ ((krow >> 1) & 7)) << 4));
@@ -517,13 +500,6 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_kernel(const T* __restrict_
     for (int kt = 0; kt < NKT; ++kt) {
       if (!HAS_BIAS && (kt + 1) * 32 <= L) {
 #pragma unroll
-#ifdef ATTN_NO_PK
-        for (int r = 0; r < 16; ++r) {
-          const float pr = __builtin_amdgcn_exp2f(fmaf(s[kt][r], sl, -m));
-          s[kt][r] = pr;
-          sum2.x += pr;
-        }
-#else
         for (int r = 0; r < 16; r += 2) {
           const f32x2v_t x = (f32x2v_t){s[kt][r], s[kt][r + 1]} * sl2 + nm2;   // v_pk_fma_f32
           const f32x2v_t pr = {__builtin_amdgcn_exp2f(x.x), __builtin_amdgcn_exp2f(x.y)};
@@ -531,7 +507,6 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_kernel(const T* __restrict_
           s[kt][r + 1] = pr.y;
           sum2 += pr;
         }
-#endif
       } else {
 #pragma unroll
         for (int rq = 0; rq < 4; ++rq) {
@@ -609,12 +584,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_kernel(const T* __restrict_
     for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
       for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
-#ifdef ATTN_NO_PIPE_V   // (measurement builds, tools/build_attn_variants.sh)
-    pv_tiles<T, NKT>(o, s, Vs, lane);
-#else
-    if constexpr (NKT <= 7) pv_tiles_pipelined<T, NKT, ATTN_PDV>(o, s, Vs, lane);
+    if constexpr (NKT <= 7) pv_tiles_pipelined<T, NKT, PV_RING>(o, s, Vs, lane);
     else pv_tiles<T, NKT>(o, s, Vs, lane);
-#endif
     if constexpr (CLS) {
       if (qt == cls_tile) {   // the CLS row in fp32: the parts' output columns added up in lane c0 (both d halves: lanes c0 and c0 + 32)
         float* dst = cls_out + (int64_t)b * H * HD + h * HD;
@@ -673,11 +644,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_kernel(const T* __restrict_
     }
   };
 
-#ifdef ATTN_NO_KV_SPLIT
-  bool v_pending = false;
-#else
   bool v_pending = true;   // (wave-uniform) the V image has not been waited for yet: every wave takes that barrier exactly once
-#endif
   while (has) {
     scores();
     if (v_pending) {
@@ -874,11 +841,7 @@ int launch_attn16(const void* qkv, void* out, int batch, int L, int H, float sca
   // query runs the third one with cls_q == nullptr (the CLS code is skipped by a wave-uniform test): the <no CLS, dropout> form is the one
   // instantiation the register allocator does not get through without spilling (224-420 bytes of scratch at 7 / 8 key tiles, ROCm 7.2).
   if (drop_seed) ALPRO_ATTN16_GO(true, true);
-#ifdef ATTN_CLS_FORCE_TPL  // (measurement builds: the instantiation with the CLS code on launches without a CLS query -- what does the code cost the regular rows?)
-  else if (true) ALPRO_ATTN16_GO(true, false);
-#else
   else if (cls_q) ALPRO_ATTN16_GO(true, false);
-#endif
   else ALPRO_ATTN16_GO(false, false);
 #undef ALPRO_ATTN16_GO
   return check_launch("alpro_attn_fwd");

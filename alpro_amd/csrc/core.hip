@@ -22,19 +22,13 @@ namespace {
 const char* const kOptNames[OPT_COUNT] = {"gemm_tile", "gemm_grid", "gemm_tune", "tn_splits", "tn_kind", "gemm_tail", "attn_bwd", "attn_order", "gemm_kind", "cu_budget", "ln_grid", "gemm_sched", "gemm_epi"};
 const char* const kOptEnv[OPT_COUNT] = {"ALPRO_GEMM_TILE", "ALPRO_GEMM_GRID", "ALPRO_GEMM_TUNE", "ALPRO_TN_SPLITS", "ALPRO_TN_KIND", "ALPRO_GEMM_TAIL", "ALPRO_ATTN_BWD", "ALPRO_ATTN_ORDER", "ALPRO_GEMM_KIND", "ALPRO_CU_BUDGET", "ALPRO_LN_GRID", "ALPRO_GEMM_SCHED", "ALPRO_GEMM_EPI"};
 int g_opts[OPT_COUNT];
-// Values that change RESULTS (gemm_tune 3 / 4 / 10 / 11 / 12: epilogue / synchronisation ablations; tn_kind 1: weight gradient without
-// its epilogue) exist only in the measurement build (-DALPRO_ABLATIONS, `python -m alpro_amd.build --ablations`, used by tools/); the
-// product library refuses them, from alpro_hip_set_option and from the environment alike.
+// Values that once selected ablations (gemm_tune >= 3, tn_kind 1, attn_bwd 3 / 4: measurement variants that have been removed) are
+// refused, from alpro_hip_set_option, alpro_hip_set_stream_option and the environment alike.
 bool option_allowed(int which, int value) {
-#ifdef ALPRO_ABLATIONS
-  (void)which; (void)value;
-  return true;
-#else
   if (which == OPT_GEMM_TUNE) return value >= 0 && value <= 2;
-  if (which == OPT_TN_KIND) return value == 0 || value == 2;   // 1: no epilogue (timing only, measurement build); 2: two-group schedule
-  if (which == OPT_ATTN_BWD) return value >= 0 && value <= 2;   // 3 / 4: the persistent key-owned backward, compiled into the measurement build only (round 4)
+  if (which == OPT_TN_KIND) return value == 0 || value == 2;   // 0: one group, 2: two-group schedule
+  if (which == OPT_ATTN_BWD) return value >= 0 && value <= 2;   // 0 two-phase, 1 best per shape, 2 key-owned
   return value >= 0;
-#endif
 }
 struct OptInit {
   OptInit() {
@@ -45,7 +39,7 @@ struct OptInit {
                                           : 0;
       g_opts[i] = e ? atoi(e) : dflt;
       if (!option_allowed(i, g_opts[i])) {
-        fprintf(stderr, "libalpro_hip: %s=%d is a result-corrupting ablation and is not part of this build (ignored)\n", kOptEnv[i], g_opts[i]);
+        fprintf(stderr, "libalpro_hip: %s=%d selected an ablation that has been removed (ignored)\n", kOptEnv[i], g_opts[i]);
         g_opts[i] = dflt;
       }
     }
@@ -634,7 +628,7 @@ extern "C" int alpro_hip_set_option(const char* name, int value) {
   for (int i = 0; name && i < OPT_COUNT; ++i)
     if (!strcmp(name, kOptNames[i])) {
       if (!option_allowed(i, value)) {
-        set_error("alpro_hip_set_option: %s=%d is an ablation / measurement-only variant, only available in the measurement build (-DALPRO_ABLATIONS)", name, value);
+        set_error("alpro_hip_set_option: %s=%d selected an ablation that has been removed; it is not a valid value", name, value);
         return ALPRO_ERR_INVALID;
       }
       __atomic_store_n(&g_opts[i], value, __ATOMIC_RELAXED);
@@ -654,7 +648,7 @@ extern "C" int alpro_hip_set_stream_option(void* stream, const char* name, int v
     return ALPRO_ERR_INVALID;
   }
   if (value >= 0 && !option_allowed(which, value)) {
-    set_error("alpro_hip_set_stream_option: %s=%d is an ablation / measurement-only variant, only available in the measurement build (-DALPRO_ABLATIONS)", name, value);
+    set_error("alpro_hip_set_stream_option: %s=%d selected an ablation that has been removed; it is not a valid value", name, value);
     return ALPRO_ERR_INVALID;
   }
   SpinGuard g;

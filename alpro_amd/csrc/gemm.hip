@@ -244,7 +244,7 @@ __device__ __forceinline__ void epi_prefetch_res(const alpro_gemm_desc_t& g, int
 // row scale of a pass comes from SCALAR loads: a pass covers 8 consecutive rows, which lie in at most two groups when row_scale_group >= 8
 // (launcher: drop-path scales per 8-frame token group, per 197-token frame, per clip) -- one wave-uniform division, two s_load_dword, a
 // compare per lane.  The plain GEMMs (qkv, fc1, dgrads) have no load at all in their passes: the stores stream.
-template <typename T, int ACT, int PASSES = 2, int ABL = 0, bool RES = true>
+template <typename T, int ACT, int PASSES = 2, bool RES = true>
 __device__ __forceinline__ void epi_rows16_c16(const alpro_gemm_desc_t& g, const float* stage, int m_base, int n_base, int lane, const float (&bias)[8],
                                                const u32x4* pre_c2 = nullptr) {
   const int c8 = (lane & 7) * 8;
@@ -320,12 +320,7 @@ __device__ __forceinline__ void epi_rows16_c16(const alpro_gemm_desc_t& g, const
         v[0] += r0.x; v[1] += r0.y; v[2] += r0.z; v[3] += r0.w; v[4] += r1.x; v[5] += r1.y; v[6] += r1.z; v[7] += r1.w;
       }
     }
-    if (ABL == 1) {  // ablation (gemm_tune 3): everything but the global store
-      u32x4 keep = pack_chunk<T>(v);
-      asm volatile("" ::"v"(keep));
-    } else {
-      __builtin_nontemporal_store(pack_chunk<T>(v), (u32x4*)((T*)g.C + m * g.ldc + n));
-    }
+    __builtin_nontemporal_store(pack_chunk<T>(v), (u32x4*)((T*)g.C + m * g.ldc + n));
   }
 }
 
@@ -510,11 +505,9 @@ constexpr int EPI_BYTES = 8 * 16 * 64 * 4;  // 32 KiB: 8 waves x (16 rows x 64 c
 //   1  copy c after MFMA 2c+1 / 2c+2: all pieces out in the first half of the step (default: +3-5 % on every shape,
 //      round-2 A/B of the variants on the model shapes)
 //   2  copy c after MFMA 3c+1 / 3c+2: first three quarters
-//   3, 4  ablations of the 16-bit-output epilogue (no global stores / no epilogue at all; wrong results by construction) -- the
-//      measurements and the three epilogue rewrites they led to are in profiles/r2_gemm_epilogue_experiments.txt
 __device__ __forceinline__ constexpr int copy_slot(int tune, int q, int pos) {
   if (tune == 0) return ((q & 1) && ((q >> 1) & 1) == pos) ? (q >> 2) : -1;
-  if (tune == 1 || tune >= 3) { const int r = q - 1 - pos; return (r >= 0 && r < 16 && (r & 1) == 0) ? (r >> 1) : -1; }
+  if (tune == 1) { const int r = q - 1 - pos; return (r >= 0 && r < 16 && (r & 1) == 0) ? (r >> 1) : -1; }
   const int r = q - 1 - pos;
   return (r >= 0 && r < 24 && r % 3 == 0) ? r / 3 : -1;
 }
@@ -621,16 +614,8 @@ __global__ __launch_bounds__(NT2, 2) void gemm_nt256p_kernel(const alpro_gemm_de
         for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
     for (int kt = 0; kt < nk; ++kt) {
       const int cur = s0 ^ (kt & 1);
-      if constexpr (TUNE == 10) {          // ablation: NO synchronisation in the K loop (races by construction): what any re-ordering of
-        if (kt == nk) block_sync();        // waits / barriers could gain at most; TUNE == 11: barrier only, TUNE == 12: DMA wait only
-      } else if constexpr (TUNE == 11) {
-        block_sync();
-      } else if constexpr (TUNE == 12) {
-        if (kt >= 2) wait_vm0();
-      } else {
       if (kt >= 2) wait_vm0();  // own pieces of K-tile kt (issued one step ago); at kt == 2 also the previous tile's stores
       block_sync();             // K-tile kt visible to everyone; everyone is done with K-tile kt-1
-      }
       // The buffer of K-tile kt-1 is free from here on: its 8 copies (K-tile kt+1, or K-tile 0 of the NEXT tile on the
       // last step) are issued BETWEEN this step's 32 MFMAs, and the two waves that share a SIMD (w, w+4) use alternating
       // slots -- a copy stalls its wave ~60-150 cycles at issue, which the partner's MFMAs cover; issued back to back by
@@ -666,10 +651,6 @@ __global__ __launch_bounds__(NT2, 2) void gemm_nt256p_kernel(const alpro_gemm_de
 #pragma unroll
           for (int i = 0; i < 4; ++i) fa[(s + 1) & 1][i] = *(const u32x4*)(cA + lds_off(a_row[i], 2 * (s + 1) + khalf));
         }
-        // measurement build, TUNE 5 / 6: raise this wave's issue priority over its SIMD partner's for the 8 MFMAs of the sub-step (the partner
-        // is then reading fragments or issuing copies), back to 0 for the fragment reads.  Measured neutral (round 3,
-        // profiles/r3_gemm_setprio_experiment.txt): 971-998 TF/s against 986-1004 on the long shapes, bit-identical results
-        if constexpr (TUNE == 5 || TUNE == 6) __builtin_amdgcn_s_setprio(TUNE == 5 ? 1 : 3);
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -681,7 +662,6 @@ __global__ __launch_bounds__(NT2, 2) void gemm_nt256p_kernel(const alpro_gemm_de
               if (copy_slot(TUNE, q, 1) >= 0 && pos == 1) copy_piece(copy_slot(TUNE, q, 1), ckt, cur ^ 1, copy_half);
             }
           }
-        if constexpr (TUNE == 5 || TUNE == 6) __builtin_amdgcn_s_setprio(0);
       }
     }
     block_sync();  // everyone is done with the last K-tile: its buffer takes the next tile's K-tile 1
@@ -749,20 +729,15 @@ __global__ __launch_bounds__(NT2, 2) void gemm_nt256p_kernel(const alpro_gemm_de
             pring[0] = load_pre(0);
             pring[1] = load_pre(1);
           }
-          if constexpr (TUNE == 4) {  // ablation: no epilogue at all (accumulators kept live)
 #pragma unroll
-            for (int i = 0; i < 4; ++i) asm volatile("" ::"v"(acc[i][0]), "v"(acc[i][1]));
-          } else {
+          for (int i = 0; i < 4; ++i) {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-#pragma unroll
-              for (int q = 0; q < 4; ++q) {
-                const int c = i * 4 + q;
-                if (READS_C2 && c + 2 < 16) pring[(c + 2) % 3] = load_pre(c + 2);
-                float* st = stage + (c & 1) * 512;
-                stage_chunk(st, acc[i][0], acc[i][1], q);
-                epi_rows16_c16<T, ACT, 1, (TUNE == 3 ? 1 : 0)>(g, st, mb + c * 8, nb, lane, bias8, READS_C2 ? &pring[c % 3] : nullptr);
-              }
+            for (int q = 0; q < 4; ++q) {
+              const int c = i * 4 + q;
+              if (READS_C2 && c + 2 < 16) pring[(c + 2) % 3] = load_pre(c + 2);
+              float* st = stage + (c & 1) * 512;
+              stage_chunk(st, acc[i][0], acc[i][1], q);
+              epi_rows16_c16<T, ACT, 1>(g, st, mb + c * 8, nb, lane, bias8, READS_C2 ? &pring[c % 3] : nullptr);
             }
           }
         }
@@ -1422,7 +1397,7 @@ __global__ __launch_bounds__(NT2, 2) __attribute__((amdgpu_num_vgpr(127))) void 
               if (!rows_ok(mf)) break;   // ragged last tile row: fragment rows at or beyond M are not stored (M % 16 == 0: launcher)
               if (READS_C2 && mf + PD < 8 && rows_ok(mf + PD)) load_pre(mf + PD, pring[(mf + PD) % RING]);
               stage_rows(mf);
-              epi_rows16_c16<T, ACT, 2, 0, RES>(g, stage, mb + mf * 16, nb, le, bias8, READS_C2 ? pring[mf % RING] : nullptr);
+              epi_rows16_c16<T, ACT, 2, RES>(g, stage, mb + mf * 16, nb, le, bias8, READS_C2 ? pring[mf % RING] : nullptr);
               if constexpr (!RES && !READS_C2) {
                 if (mf == 0) early_ticket();
               }
@@ -1525,15 +1500,6 @@ int launch_gemm_inst(const alpro_gemm_desc_t& g, hipStream_t st) {
     if constexpr (std::is_same<T, bf16_t>::value && ACT == ALPRO_ACT_NONE && MAP == ALPRO_MAP_IDENTITY) {
       (void)hipFuncSetAttribute((const void*)gemm_nt256p_kernel<T, ACT, MAP, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TILE2_BYTES + EPI_BYTES);
       (void)hipFuncSetAttribute((const void*)gemm_nt256p_kernel<T, ACT, MAP, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TILE2_BYTES + EPI_BYTES);
-#ifdef ALPRO_ABLATIONS  // result-corrupting measurement variants: only in the tools/ build (python -m alpro_amd.build --ablations)
-      (void)hipFuncSetAttribute((const void*)gemm_nt256p_kernel<T, ACT, MAP, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TILE2_BYTES + EPI_BYTES);
-      (void)hipFuncSetAttribute((const void*)gemm_nt256p_kernel<T, ACT, MAP, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TILE2_BYTES + EPI_BYTES);
-      (void)hipFuncSetAttribute((const void*)gemm_nt256p_kernel<T, ACT, MAP, 12>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TILE2_BYTES + EPI_BYTES);
-      (void)hipFuncSetAttribute((const void*)gemm_nt256p_kernel<T, ACT, MAP, 11>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TILE2_BYTES + EPI_BYTES);
-      (void)hipFuncSetAttribute((const void*)gemm_nt256p_kernel<T, ACT, MAP, 10>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TILE2_BYTES + EPI_BYTES);
-      (void)hipFuncSetAttribute((const void*)gemm_nt256p_kernel<T, ACT, MAP, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TILE2_BYTES + EPI_BYTES);   // setprio variants
-      (void)hipFuncSetAttribute((const void*)gemm_nt256p_kernel<T, ACT, MAP, 6>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TILE2_BYTES + EPI_BYTES);
-#endif
     }
   });
   const int big_tiles = ((g.N + BN2 - 1) / BN2) * ((g.M + BM2 - 1) / BM2);
@@ -1621,15 +1587,6 @@ int launch_gemm_inst(const alpro_gemm_desc_t& g, hipStream_t st) {
     if constexpr (std::is_same<T, bf16_t>::value && ACT == ALPRO_ACT_NONE && MAP == ALPRO_MAP_IDENTITY) {
       if (tune == 0) { hipLaunchKernelGGL((gemm_nt256p_kernel<T, ACT, MAP, 0>), dim3(grid), dim3(NT2), 4 * TILE2_BYTES + EPI_BYTES, st, g, tail); return check_launch("alpro_gemm"); }
       if (tune == 2) { hipLaunchKernelGGL((gemm_nt256p_kernel<T, ACT, MAP, 2>), dim3(grid), dim3(NT2), 4 * TILE2_BYTES + EPI_BYTES, st, g, tail); return check_launch("alpro_gemm"); }
-#ifdef ALPRO_ABLATIONS
-      if (tune == 3) { hipLaunchKernelGGL((gemm_nt256p_kernel<T, ACT, MAP, 3>), dim3(grid), dim3(NT2), 4 * TILE2_BYTES + EPI_BYTES, st, g, tail); return check_launch("alpro_gemm"); }
-      if (tune == 4) { hipLaunchKernelGGL((gemm_nt256p_kernel<T, ACT, MAP, 4>), dim3(grid), dim3(NT2), 4 * TILE2_BYTES + EPI_BYTES, st, g, tail); return check_launch("alpro_gemm"); }
-      if (tune == 12) { hipLaunchKernelGGL((gemm_nt256p_kernel<T, ACT, MAP, 12>), dim3(grid), dim3(NT2), 4 * TILE2_BYTES + EPI_BYTES, st, g, tail); return check_launch("alpro_gemm"); }
-      if (tune == 11) { hipLaunchKernelGGL((gemm_nt256p_kernel<T, ACT, MAP, 11>), dim3(grid), dim3(NT2), 4 * TILE2_BYTES + EPI_BYTES, st, g, tail); return check_launch("alpro_gemm"); }
-      if (tune == 10) { hipLaunchKernelGGL((gemm_nt256p_kernel<T, ACT, MAP, 10>), dim3(grid), dim3(NT2), 4 * TILE2_BYTES + EPI_BYTES, st, g, tail); return check_launch("alpro_gemm"); }
-      if (tune == 5) { hipLaunchKernelGGL((gemm_nt256p_kernel<T, ACT, MAP, 5>), dim3(grid), dim3(NT2), 4 * TILE2_BYTES + EPI_BYTES, st, g, tail); return check_launch("alpro_gemm"); }
-      if (tune == 6) { hipLaunchKernelGGL((gemm_nt256p_kernel<T, ACT, MAP, 6>), dim3(grid), dim3(NT2), 4 * TILE2_BYTES + EPI_BYTES, st, g, tail); return check_launch("alpro_gemm"); }
-#endif
     }
     hipLaunchKernelGGL((gemm_nt256p_kernel<T, ACT, MAP>), dim3(grid), dim3(NT2), 4 * TILE2_BYTES + EPI_BYTES, st, g, tail);
   } else {

@@ -57,7 +57,7 @@ template <typename T, int PP = 0>
 __global__ __launch_bounds__(NT3, 1) void gemm_tn_kernel(const T* __restrict__ A, int64_t lda, const T* __restrict__ B, int64_t ldb,
                                                          float* __restrict__ C, int64_t ldc, int M, int N, int K, int per,
                                                          int tiles, int units, int tn_cnt, float* __restrict__ colsum, float* __restrict__ part,
-                                                         float* __restrict__ part_cs, int ablate) {
+                                                         float* __restrict__ part_cs, int ablate /* unused, always 0: keeps the kernel-argument layout */) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave >> 2, wc = wave & 3;
@@ -273,9 +273,6 @@ __global__ __launch_bounds__(NT3, 1) void gemm_tn_kernel(const T* __restrict__ A
     else if (lane < 32 && n < N) unsafeAtomicAdd(colsum + n, t);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // drain the tail copies (zero page) before the wave exits
-#ifdef ALPRO_ABLATIONS
-  if (ablate == 1 && acc[0][0][0] != 12345.f) return;  // measurement only (tn_kind 1, tools/ build): no epilogue, results are garbage
-#endif
   if (part) {
     // Workspace mode: the partial tile goes out in accumulator order -- 16 bytes per lane, 1 KiB per wave instruction, 32 plain
     // stores per lane instead of 128 fabric atomics -- and tn_reduce_kernel adds the partials of a tile to C in a fixed order.
@@ -489,13 +486,7 @@ extern "C" int alpro_gemm_tn_acc_ws(const void* A, int64_t lda, const void* B, i
     part = p.ranges > 1 ? (float*)workspace : nullptr;
     part_cs = colsum ? (float*)workspace + p.part_floats : nullptr;
   }
-  const int kind_opt = get_option(OPT_TN_KIND);
-  const bool pp = kind_opt == 2;             // 2: the two-group schedule (round 4), result-preserving
-#ifdef ALPRO_ABLATIONS
-  const int kind = kind_opt == 1 ? 1 : 0;    // 1: no epilogue (timing only; measurement build)
-#else
-  const int kind = 0;
-#endif
+  const bool pp = get_option(OPT_TN_KIND) == 2;   // 2: the two-group schedule (round 4), result-preserving
   const unsigned grid = (unsigned)((p.units + 7) / 8 * 8);
   const size_t lds = (size_t)NSTAGE * 2 * IMG_BYTES;
   hipStream_t st = (hipStream_t)stream;
@@ -505,18 +496,18 @@ extern "C" int alpro_gemm_tn_acc_ws(const void* A, int64_t lda, const void* B, i
       (void)hipFuncSetAttribute((const void*)gemm_tn_kernel<bf16_t, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       (void)hipFuncSetAttribute((const void*)gemm_tn_kernel<bf16_t, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     });
-    if (pp) hipLaunchKernelGGL((gemm_tn_kernel<bf16_t, 1>), dim3(grid), dim3(NT3), lds, st, (const bf16_t*)A, lda, (const bf16_t*)B, ldb, C, ldc, M, N, K, p.per, p.tiles, p.units, p.tn, colsum, part, part_cs, kind);
-    else hipLaunchKernelGGL((gemm_tn_kernel<bf16_t, 0>), dim3(grid), dim3(NT3), lds, st, (const bf16_t*)A, lda, (const bf16_t*)B, ldb, C, ldc, M, N, K, p.per, p.tiles, p.units, p.tn, colsum, part, part_cs, kind);
+    if (pp) hipLaunchKernelGGL((gemm_tn_kernel<bf16_t, 1>), dim3(grid), dim3(NT3), lds, st, (const bf16_t*)A, lda, (const bf16_t*)B, ldb, C, ldc, M, N, K, p.per, p.tiles, p.units, p.tn, colsum, part, part_cs, 0);
+    else hipLaunchKernelGGL((gemm_tn_kernel<bf16_t, 0>), dim3(grid), dim3(NT3), lds, st, (const bf16_t*)A, lda, (const bf16_t*)B, ldb, C, ldc, M, N, K, p.per, p.tiles, p.units, p.tn, colsum, part, part_cs, 0);
   } else {
     static DeviceOnce once;
     once.run([&] {
       (void)hipFuncSetAttribute((const void*)gemm_tn_kernel<f16_t, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       (void)hipFuncSetAttribute((const void*)gemm_tn_kernel<f16_t, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     });
-    if (pp) hipLaunchKernelGGL((gemm_tn_kernel<f16_t, 1>), dim3(grid), dim3(NT3), lds, st, (const f16_t*)A, lda, (const f16_t*)B, ldb, C, ldc, M, N, K, p.per, p.tiles, p.units, p.tn, colsum, part, part_cs, kind);
-    else hipLaunchKernelGGL((gemm_tn_kernel<f16_t, 0>), dim3(grid), dim3(NT3), lds, st, (const f16_t*)A, lda, (const f16_t*)B, ldb, C, ldc, M, N, K, p.per, p.tiles, p.units, p.tn, colsum, part, part_cs, kind);
+    if (pp) hipLaunchKernelGGL((gemm_tn_kernel<f16_t, 1>), dim3(grid), dim3(NT3), lds, st, (const f16_t*)A, lda, (const f16_t*)B, ldb, C, ldc, M, N, K, p.per, p.tiles, p.units, p.tn, colsum, part, part_cs, 0);
+    else hipLaunchKernelGGL((gemm_tn_kernel<f16_t, 0>), dim3(grid), dim3(NT3), lds, st, (const f16_t*)A, lda, (const f16_t*)B, ldb, C, ldc, M, N, K, p.per, p.tiles, p.units, p.tn, colsum, part, part_cs, 0);
   }
-  if ((part || part_cs) && kind != 1)
+  if (part || part_cs)
     hipLaunchKernelGGL(tn_reduce_kernel, dim3((part ? p.tiles * 64 : 0) + (part_cs ? p.tn * (TW / 32) : 0)), dim3(256), 0, st, part, part_cs, C, ldc, colsum, N, K, p.tiles, p.ranges, p.tn);
   return check_launch("alpro_gemm_tn_acc");
 }

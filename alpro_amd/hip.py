@@ -9,7 +9,7 @@ import os
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("ALPRO_HIP_LIB") or os.path.join(_HERE, "lib", "libalpro_hip.so")  # ALPRO_HIP_LIB: tools/ load the ablation build
+LIB_PATH = os.environ.get("ALPRO_HIP_LIB") or os.path.join(_HERE, "lib", "libalpro_hip.so")  # ALPRO_HIP_LIB: another build of the library
 
 F32, BF16, F16 = 0, 1, 2
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_GELU_BWD, ACT_GELU_SAVE_GRAD, ACT_MUL_SAVED, ACT_RELU_MASK = 0, 1, 2, 3, 4, 5, 6
@@ -156,9 +156,8 @@ _option_values = {}
 
 def set_option(name, value):
     """Measurement knob of the library (alpro_hip_set_option): 'attn_bwd' (16-bit attention backward with 5-8 key tiles: 0 two-phase,
-    1 = default, best per shape, 2 key-owned; 3 / 4, the persistent key-owned variants, only in the --ablations build), 'gemm_tile', 'gemm_grid',
-    'gemm_tune', 'gemm_kind' (identity-map 16-bit shapes: 0 = round-3 persistent kernel, 1 = 8-phase two-group kernel, the default), 'tn_splits'
-    (token ranges of the weight-gradient GEMM), 'tn_kind' (0, 2 = two-group schedule; 1 = no wgrad epilogue, --ablations build only), 'cu_budget'
+    1 = default, best per shape, 2 key-owned), 'gemm_tile', 'gemm_grid', 'gemm_tune' (0-2), 'gemm_kind' (identity-map 16-bit shapes: 0 = round-3 persistent kernel, 1 = 8-phase two-group kernel, the default), 'tn_splits'
+    (token ranges of the weight-gradient GEMM), 'tn_kind' (0, 2 = two-group schedule), 'cu_budget'
     (CUs the persistent grids are sized for; 0 = all), 'ln_grid' (cap on the LayerNorm backward's workgroup count; 0 = the default plan),
     'gemm_sched' (8-phase GEMM: 1 = tiles from per-XCD ticket counters, the default; 0 = the static round-robin walk; results are bitwise equal)."""
     _check(load().alpro_hip_set_option(name.encode(), int(value)), "alpro_hip_set_option")

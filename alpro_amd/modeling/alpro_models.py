@@ -202,8 +202,7 @@ class AlproBaseModel(nn.Module):
         video_embeds_all = torch.cat([video_embeds, video_embeds[neg_video], video_embeds], dim=0)
         video_atts_all = torch.cat([video_atts, video_atts, video_atts], dim=0)
         bert = self.text_encoder.bert if hasattr(self.text_encoder, "bert") else self.text_encoder
-        if (cls_only and os.environ.get("ALPRO_FUSION_TAIL_ROWS", "1") != "0" and text_embeds.is_cuda
-                and getattr(bert.encoder.layer[-1], "fuse_residual_ln", False)):
+        if cls_only and os.environ.get("ALPRO_FUSION_TAIL_ROWS", "1") != "0" and text_embeds.is_cuda:
             seq_len = text_embeds_all.shape[1] + video_embeds_all.shape[1]
             rows = torch.arange(3 * bs, device=device, dtype=torch.long) * seq_len
             vl_embeddings = bert(encoder_embeds=torch.cat([text_embeds_all, video_embeds_all], dim=1), attention_mask=torch.cat([text_atts_all, video_atts_all], dim=1),
@@ -225,7 +224,6 @@ class AlproForPretrain(AlproBaseModel):
         self.prompter = Prompter(config, video_enc_cfg)  # frozen teacher for pseudo labels
         self.use_mask_prob = 0
         self.batch_encoder_passes = True  # one 4B fusion pass / one 2B text pass instead of the reference's 3 / 2 calls
-        self.gather_fusion_input = os.environ.get("ALPRO_GATHER_FUSION", "1") != "0"   # the 4B fusion batch as a row gather (alpro_gather_seq_*), 0 = torch.cat + autograd (A/B)
         # Round 6 (third session): the LAST fusion layer's row-wise tail (attention-output dense, LayerNorms, FFN) only on the rows the heads read -- the 3B
         # [CLS] rows, the MLM pairs' text rows, the positives' patch rows: 239 of every 948 rows of the 4B x 237 batch; nothing else of that layer's output
         # reaches a loss (alpro_models.py:283,331-338,366-371,215-218), forward or backward.  ALPRO_FUSION_TAIL_ROWS=0: every row, as before (A/B).
@@ -300,35 +298,27 @@ class AlproForPretrain(AlproBaseModel):
             else:
                 torch.cuda.current_stream(device).wait_stream(text_side)
                 both.record_stream(torch.cuda.current_stream(device))   # allocated on the side stream, read (and possibly outlived) on this one
-            text_embeds, mlm_text_embeds = both[:b], both[b:]
-            text_feat = self._text_feat(text_embeds)
+            text_feat = self._text_feat(both[:b])
             vtc_loss, sim_v2t, sim_t2v, _ = self._vtc(video_feat, text_feat)
             neg_video, neg_text = self._sample_negatives(sim_v2t, sim_t2v, b)
             ta_all = torch.cat([text_atts, text_atts, text_atts[neg_text], text_atts], dim=0)
             va_all = torch.cat([video_atts] * 4, dim=0)
-            if self.gather_fusion_input:
-                # sequence s of the 4B fusion batch = [text pool row ti[s] ; video pool row vi[s]] over the pools (both = [captions ; masked captions],
-                # video_embeds): positives, negative videos, negative texts, MLM pairs -- the rows the reference's cats hold, never materialised by torch
-                ar = torch.arange(b, device=device)
-                ti = torch.cat([ar, ar, neg_text, ar + b])
-                vi = torch.cat([ar, neg_video, ar, ar])
-                txt_len_, seq_len_ = text_atts.shape[1], text_atts.shape[1] + video_embeds.shape[1]
-                tail = use_mpm and self.fusion_tail_rows and getattr(self.text_encoder.bert.encoder.layer[-1], 'fuse_residual_ln', False)
-                rows = self._fusion_out_rows(b, txt_len_, seq_len_, device) if tail else None
-                fused = self.text_encoder.bert(encoder_embeds_parts=(both, video_embeds, ti, vi), attention_mask=torch.cat([ta_all, va_all], dim=1), return_dict=True,
-                                               mode='fusion', out_rows=rows).last_hidden_state
-            else:
-                t_all = torch.cat([text_embeds, text_embeds, text_embeds[neg_text], mlm_text_embeds], dim=0)
-                v_all = torch.cat([video_embeds, video_embeds[neg_video], video_embeds, video_embeds], dim=0)
-                fused = self._fusion(torch.cat([t_all, v_all], dim=1), torch.cat([ta_all, va_all], dim=1))
-            txt_len = text_atts.shape[1]
-            if self.gather_fusion_input and use_mpm and rows is not None:
+            # sequence s of the 4B fusion batch = [text pool row ti[s] ; video pool row vi[s]] over the pools (both = [captions ; masked captions],
+            # video_embeds): positives, negative videos, negative texts, MLM pairs -- the rows the reference's cats hold, never materialised by torch
+            ar = torch.arange(b, device=device)
+            ti = torch.cat([ar, ar, neg_text, ar + b])
+            vi = torch.cat([ar, neg_video, ar, ar])
+            txt_len, seq_len = text_atts.shape[1], text_atts.shape[1] + video_embeds.shape[1]
+            rows = self._fusion_out_rows(b, txt_len, seq_len, device) if (use_mpm and self.fusion_tail_rows) else None
+            fused = self.text_encoder.bert(encoder_embeds_parts=(both, video_embeds, ti, vi), attention_mask=torch.cat([ta_all, va_all], dim=1), return_dict=True,
+                                           mode='fusion', out_rows=rows).last_hidden_state
+            if rows is not None:
                 # `fused` holds only the rows the heads read, in this order (see _fusion_out_rows): 3B [CLS] rows | B x txt_len MLM text rows | B x N patch rows
                 n_cls, n_mlm = 3 * b, b * txt_len
                 cls_rows, mlm_rows = fused[:n_cls], fused[n_cls:n_cls + n_mlm].view(b, txt_len, -1)
                 pos_patch_rows = fused[n_cls + n_mlm:].view(b, -1, fused.shape[-1])
                 encoder_outputs_pos = None
-            elif self.gather_fusion_input and use_mpm:
+            elif use_mpm:
                 cls_rows, mlm_rows, pos_patch_rows = _FusionOutputs.apply(fused, b, txt_len)
                 encoder_outputs_pos = None
             else:
@@ -643,7 +633,7 @@ class AlproForSequenceClassification(AlproBaseModel):
         att = torch.ones((S, L), dtype=text_input_mask.dtype, device=text_input_mask.device)
         att[:, :Lt] = text_input_mask[ti]
         bert = self.text_encoder
-        tail = self.fusion_tail_rows and text_embeds.is_cuda and getattr(bert.encoder.layer[-1], 'fuse_residual_ln', False)
+        tail = self.fusion_tail_rows and text_embeds.is_cuda
         rows = torch.arange(S, device=ti.device, dtype=torch.long) * L if tail else None
         out = bert(encoder_embeds_parts=(text_embeds, video_embeds, ti, vi), attention_mask=att, return_dict=True, mode='fusion',
                    out_rows=rows).last_hidden_state

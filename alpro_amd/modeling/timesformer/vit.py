@@ -21,7 +21,6 @@ arguments, `forward_features` signatures and the state_dict layout (`model.block
   DropPath per (b n)/(b t)/b rows (vit_utils.py:137)   row_scale vector in the GEMM epilogue
 """
 import math
-import os
 from functools import partial
 
 import torch
@@ -221,11 +220,10 @@ class Block(nn.Module):
     # 0.9 GFLOP product), bias Wfc bp under the row scale and bfc after it (alpro_gemm bias2).  Saves one 100k x 768 x 768
     # GEMM per block in forward and, in backward, one dgrad and one wgrad: dWe = (s*dY)^T a is taken once and pushed through
     # the product rule (dWfc = dWe Wp^T + db1 bp^T, dWp = Wfc^T dWe, dbp = Wfc^T db1, dbfc = colsum(dY)).
+    # With the merged projection the residual adds of the two attention halves run inside the following LayerNorm (alpro_add_layernorm_fwd);
+    # merge_temporal_proj = False (the two Linears as written, fp32 residual in the GEMM epilogue) is the tests' oracle for it.
     merge_temporal_proj = True
-    fuse_ln_bwd_emit = os.environ.get("ALPRO_FUSE_LN_BWD", "1") != "0"   # LayerNorm backward also emits the next GEMMs' operand rows (alpro_layernorm_bwd_emit) instead of a gather_cast pass; 0 = round-2 form (A/B)
-    fuse_residual_ln = os.environ.get("ALPRO_FUSE_RESIDUAL_LN", "1") != "0"   # residual adds of the two attention halves inside the following LayerNorm (alpro_add_layernorm_fwd); 0 = round-2 form (A/B measurements)
-
-    batch_merged_tproj = os.environ.get("ALPRO_BATCH_TPROJ", "1") != "0"   # the 12 blocks' merged-projection upkeep in batched launches (_MergedTProjBank); 0 = per block (A/B)
+    batch_merged_tproj = True   # the 12 blocks' merged-projection upkeep in batched launches (_MergedTProjBank); False = per block
 
     def _bank(self):
         bank = getattr(self, "_bank_obj", None) if (self.batch_merged_tproj and self.merge_temporal_proj) else None
@@ -318,17 +316,12 @@ class Block(nn.Module):
         return self.drop_path.row_scale(rows, device)
 
     def _forward_halves_unfused(self, x, xf, a, B, T, N, H, D, dt, drop_t=None, drop_s=None):
-        """Round-2 form of the two attention halves' tails (fp32 residual read-modify-write in the GEMM epilogue, CLS side buffer);
-        kept for A/B measurements (Block.fuse_residual_ln = False) and for the unmerged temporal projection."""
+        """The two attention halves' tails with the unmerged temporal projection (merge_temporal_proj = False): fp32 residual
+        read-modify-write in the GEMM epilogue, CLS side buffer."""
         ta, sa = self.temporal_attn, self.attn
-        if self.merge_temporal_proj:
-            mg = self._merged_tproj(dt)
-            hip.gemm(a, mg["w"], out=xf, bias=mg["b1"], bias2=self.temporal_fc.bias, out_dtype=torch.float32, residual=xf,
-                     row_scale=drop_t, row_scale_group=T, map_mode=hip.MAP_SKIP_CLS, map_p0=N * T)
-        else:
-            pr = hip.gemm(a, self._w("t_proj", ta.proj, dt), bias=ta.proj.bias, row_scale=drop_t, row_scale_group=T)
-            hip.gemm(pr, self._w("t_fc", self.temporal_fc, dt), out=xf, bias=self.temporal_fc.bias, out_dtype=torch.float32,
-                     residual=xf, map_mode=hip.MAP_SKIP_CLS, map_p0=N * T)
+        pr = hip.gemm(a, self._w("t_proj", ta.proj, dt), bias=ta.proj.bias, row_scale=drop_t, row_scale_group=T)
+        hip.gemm(pr, self._w("t_fc", self.temporal_fc, dt), out=xf, bias=self.temporal_fc.bias, out_dtype=torch.float32,
+                 residual=xf, map_mode=hip.MAP_SKIP_CLS, map_p0=N * T)
         hs = hip.layernorm(x, self.norm1.weight, self.norm1.bias, VIT_EPS, dt, rows=B * T * (N + 1),
                            map_mode=hip.MAP_FRAME_TOKENS, map_p0=T, map_p1=N)
         qkv = hip.gemm(hs, self._w("s_qkv", sa.qkv, dt), bias=sa.qkv.bias)
@@ -348,7 +341,7 @@ class Block(nn.Module):
         xf = x.view(B * S, D)
         ta, sa = self.temporal_attn, self.attn
         drop_t, drop_s, drop_m = self._drop(B * N, x.device), self._drop(B * T, x.device), self._drop(B, x.device)
-        cp = rt.cls_precise(dt) and self.fuse_residual_ln and self.merge_temporal_proj
+        cp = rt.cls_precise(dt) and self.merge_temporal_proj
         side = _ClsSide.get(x.device) if (cp and rt.cls_stream(False) and x.is_cuda) else None
         if side is not None:
             x_cls_in, cls_q, o_c_buf = self._cls_side_begin(side, x, B, T, snapshot=True)
@@ -364,7 +357,7 @@ class Block(nn.Module):
         else:
             qkv = hip.gemm(h, self._w("t_qkv", ta.qkv, dt), bias=ta.qkv.bias)
             a = hip.attn_temporal(qkv, T, H, ta.scale)
-        if self.fuse_residual_ln and self.merge_temporal_proj:
+        if self.merge_temporal_proj:
             # round 3: the two N = 768 projections write 16-bit deltas in plain row order; residual add + row maps + LayerNorm are one
             # streaming kernel each (alpro_add_layernorm_fwd) -- see the kernel's header comment in csrc/core.hip
             mg = self._merged_tproj(dt)
@@ -415,7 +408,7 @@ class Block(nn.Module):
         sv = {"x": x, "dims": (B, T, N, S, D, H), "dt": dt}
         sv["drop_t"], sv["drop_s"], sv["drop_m"] = self._drop(B * N, dev), self._drop(B * T, dev), self._drop(B, dev)
         cside = None
-        if rt.cls_precise(dt) and rt.cls_stream(True) and x.is_cuda and self.fuse_residual_ln and self.merge_temporal_proj:
+        if rt.cls_precise(dt) and rt.cls_stream(True) and x.is_cuda and self.merge_temporal_proj:
             cside = _ClsSide.get(dev)
             x_cls_in, cls_q, o_c_buf = self._cls_side_begin(cside, x, B, T, snapshot=False)
         h = hip.layernorm(x, self.temporal_norm1.weight, self.temporal_norm1.bias, VIT_EPS, dt, rows=B * N * T,
@@ -427,7 +420,7 @@ class Block(nn.Module):
             qkv_t = hip.gemm(h, self._w("t_qkv", ta.qkv, dt), bias=ta.qkv.bias)
             a_t, lse_t = hip.attn_temporal(qkv_t, T, H, ta.scale, want_lse=True)
         sv["merged"] = self.merge_temporal_proj
-        if self.fuse_residual_ln and self.merge_temporal_proj:
+        if self.merge_temporal_proj:
             pr = None
             mg = self._merged_tproj(dt)
             d_t = hip.gemm(a_t, mg["w"], bias=mg["b1"], row_scale=sv["drop_t"], row_scale_group=T)
@@ -453,15 +446,9 @@ class Block(nn.Module):
         else:
             xt = torch.empty_like(x)
             xt[:, 0] = x[:, 0]
-            if self.merge_temporal_proj:
-                pr = None
-                mg = self._merged_tproj(dt)
-                hip.gemm(a_t, mg["w"], out=xt.view(B * S, D), bias=mg["b1"], bias2=self.temporal_fc.bias, out_dtype=torch.float32,
-                         residual=x.view(B * S, D), row_scale=sv["drop_t"], row_scale_group=T, map_mode=hip.MAP_SKIP_CLS, map_p0=N * T)
-            else:
-                pr = hip.gemm(a_t, self._w("t_proj", ta.proj, dt), bias=ta.proj.bias, row_scale=sv["drop_t"], row_scale_group=T)
-                hip.gemm(pr, self._w("t_fc", self.temporal_fc, dt), out=xt.view(B * S, D), bias=self.temporal_fc.bias, out_dtype=torch.float32,
-                         residual=x.view(B * S, D), map_mode=hip.MAP_SKIP_CLS, map_p0=N * T)
+            pr = hip.gemm(a_t, self._w("t_proj", ta.proj, dt), bias=ta.proj.bias, row_scale=sv["drop_t"], row_scale_group=T)
+            hip.gemm(pr, self._w("t_fc", self.temporal_fc, dt), out=xt.view(B * S, D), bias=self.temporal_fc.bias, out_dtype=torch.float32,
+                     residual=x.view(B * S, D), map_mode=hip.MAP_SKIP_CLS, map_p0=N * T)
             hs = hip.layernorm(xt, self.norm1.weight, self.norm1.bias, VIT_EPS, dt, rows=B * T * (N + 1),
                                map_mode=hip.MAP_FRAME_TOKENS, map_p0=T, map_p1=N)
             qkv_s = hip.gemm(hs, self._w("s_qkv", sa.qkv, dt), bias=sa.qkv.bias)
@@ -474,15 +461,15 @@ class Block(nn.Module):
             hip.cls_mean_residual(xt, side, x2, B, T)
             h2 = hip.layernorm(x2, self.norm2.weight, self.norm2.bias, VIT_EPS, dt)
         u, sv["u_tiled"] = tr.gelu_save_buffer(B * S, self.mlp.fc1.out_features, D, dt, dev)
-        sv["u_grad"] = tr.SAVE_GELU_GRAD   # u holds gelu'(fc1 output) (round 3) rather than the fc1 output itself (round 5: in the GEMM's tile order)
-        f1 = hip.gemm(h2, self._w("fc1", self.mlp.fc1, dt), bias=self.mlp.fc1.bias, act=hip.ACT_GELU_SAVE_GRAD if sv["u_grad"] else hip.ACT_GELU, pre_act=u,
+        # u holds gelu'(fc1 output) (round 3) rather than the fc1 output itself (round 5: in the GEMM's tile order)
+        f1 = hip.gemm(h2, self._w("fc1", self.mlp.fc1, dt), bias=self.mlp.fc1.bias, act=hip.ACT_GELU_SAVE_GRAD, pre_act=u,
                       c2_tiled=sv["u_tiled"])
         out = torch.empty_like(x)
         hip.gemm(f1, self._w("fc2", self.mlp.fc2, dt), out=out.view(B * S, D), bias=self.mlp.fc2.bias, out_dtype=torch.float32,
                  residual=x2.view(B * S, D), row_scale=sv["drop_m"], row_scale_group=S)
         if cside is not None:
             self._cls_side_finish(cside, ev_x2, torch.cuda.current_stream().record_event(), x_cls_in, o_c, B, T, sv["drop_s"], sv["drop_m"], x2[:, 0], out[:, 0])
-        elif rt.cls_precise(dt) and self.fuse_residual_ln and self.merge_temporal_proj:
+        elif rt.cls_precise(dt) and self.merge_temporal_proj:
             # precise CLS rows: the block output's CLS row and the saved pre-MLP stream's CLS row (norm2's backward input) take the fp32 values;
             # the backward differentiates the 16-bit graph as before (its CLS-row operands differ from these by one rounding)
             self._cls_chain(x[:, 0], o_c, B, T, sv["drop_s"], sv["drop_m"], x2[:, 0], out[:, 0])
@@ -507,20 +494,15 @@ class Block(nn.Module):
         else:
             qkv = hip.gemm(h, self._w("t_qkv", ta.qkv, dt), bias=ta.qkv.bias)
             a = hip.attn_temporal(qkv, T, H, ta.scale)
-        if self.fuse_residual_ln and self.merge_temporal_proj:
+        if self.merge_temporal_proj:
             mg = self._merged_tproj(dt)
             d_t = hip.gemm(a, mg["w"], bias=mg["b1"])
             hs, _ = hip.add_layernorm(x, d_t, self.norm1.weight, self.norm1.bias, VIT_EPS, mode=hip.ADD_PRE_SPATIAL, want_x=False,
                                       delta_bias=self.temporal_fc.bias, T=T, N=N)   # the patch rows of x are not read again; x[:, 0] is untouched
         else:
-            if self.merge_temporal_proj:
-                mg = self._merged_tproj(dt)
-                hip.gemm(a, mg["w"], out=xf, bias=mg["b1"], bias2=self.temporal_fc.bias, out_dtype=torch.float32, residual=xf,
-                         map_mode=hip.MAP_SKIP_CLS, map_p0=N * T)
-            else:
-                pr = hip.gemm(a, self._w("t_proj", ta.proj, dt), bias=ta.proj.bias)
-                hip.gemm(pr, self._w("t_fc", self.temporal_fc, dt), out=xf, bias=self.temporal_fc.bias, out_dtype=torch.float32,
-                         residual=xf, map_mode=hip.MAP_SKIP_CLS, map_p0=N * T)
+            pr = hip.gemm(a, self._w("t_proj", ta.proj, dt), bias=ta.proj.bias)
+            hip.gemm(pr, self._w("t_fc", self.temporal_fc, dt), out=xf, bias=self.temporal_fc.bias, out_dtype=torch.float32,
+                     residual=xf, map_mode=hip.MAP_SKIP_CLS, map_p0=N * T)
             hs = hip.layernorm(x, self.norm1.weight, self.norm1.bias, VIT_EPS, dt, rows=B * T * (N + 1),
                                map_mode=hip.MAP_FRAME_TOKENS, map_p0=T, map_p1=N)
         qkv = hip.gemm(hs, self._w("s_qkv", sa.qkv, dt), bias=sa.qkv.bias)
@@ -580,24 +562,19 @@ class Block(nn.Module):
         B, T, N, S, D, H = sv["dims"]
         dt = sv["dt"]
         ta, sa = self.temporal_attn, self.attn
-        fuse = self.fuse_ln_bwd_emit
         # ---- MLP: out = x2 + drop_m * (fc2(gelu(fc1(LN2(x2)))))
         if dz is None:
             dz = hip.gather_cast(dx, dt, row_scale=sv["drop_m"], row_scale_group=S)
         tr.wgrad(dz, sv["f1"], self.mlp.fc2.weight, self.mlp.fc2.bias)
-        du = tr.dgrad(dz, self._wt("fc2", self.mlp.fc2, dt), gelu_pre=sv["u"], gelu_saved_grad=sv.get("u_grad", False), gelu_tiled=sv.get("u_tiled", False))
+        du = tr.dgrad(dz, self._wt("fc2", self.mlp.fc2, dt), gelu_grad=sv["u"], gelu_tiled=sv["u_tiled"])
         del dz
         tr.wgrad(du, sv["h2"], self.mlp.fc1.weight, self.mlp.fc1.bias)
         dh2 = tr.dgrad(du, self._wt("fc1", self.mlp.fc1, dt))
         g, b_ = tr.grad_buffer(self.norm2.weight, zero=True)[0], tr.grad_buffer(self.norm2.bias, zero=True)[0]
         # ---- spatial: x2 = scatter(xt + drop_s * proj(attn(qkv(LN1(gather(xt)))))), CLS averaged over frames
-        if fuse:   # norm2's backward hands the finished d(x2) rows straight to the spatial projection's GEMMs (frame-token order, drop_s, CLS / T)
-            _, dpo = hip.layernorm_bwd(dh2, sv["x2"], self.norm2.weight, VIT_EPS, dx, g, b_,
-                                       emit=dict(mode=hip.EMIT_FRAME, rows=B * T * (N + 1), dtype=dt, T=T, N=N, scale=sv["drop_s"]))
-        else:
-            hip.layernorm_bwd(dh2, sv["x2"], self.norm2.weight, VIT_EPS, dx, g, b_)
-            dpo = hip.gather_cast(dx, dt, rows=B * T * (N + 1), map_mode=hip.MAP_FRAME_TOKENS, map_p0=T, map_p1=N,
-                                  row_scale=sv["drop_s"], row_scale_group=N + 1, cls_scale=1.0 / T)
+        # norm2's backward hands the finished d(x2) rows straight to the spatial projection's GEMMs (frame-token order, drop_s, CLS / T)
+        _, dpo = hip.layernorm_bwd(dh2, sv["x2"], self.norm2.weight, VIT_EPS, dx, g, b_,
+                                   emit=dict(mode=hip.EMIT_FRAME, rows=B * T * (N + 1), dtype=dt, T=T, N=N, scale=sv["drop_s"]))
         tr.wgrad(dpo, sv["a_s"], sa.proj.weight, sa.proj.bias)
         da = tr.dgrad(dpo, self._wt("s_proj", sa.proj, dt))
         del dpo
@@ -607,7 +584,7 @@ class Block(nn.Module):
         g, b_ = tr.grad_buffer(self.norm1.weight, zero=True)[0], tr.grad_buffer(self.norm1.bias, zero=True)[0]
         # ---- temporal: xt[:, 1:] = x[:, 1:] + fc(drop_t * proj(attn(qkv(LN_t(x[:, 1:])))))
         G = None
-        if fuse and sv["merged"]:  # norm1's backward emits drop_t * d(xt)[:, 1:] and the temporal_fc bias gradient (unscaled column sums)
+        if sv["merged"]:  # norm1's backward emits drop_t * d(xt)[:, 1:] and the temporal_fc bias gradient (unscaled column sums)
             _, G = hip.layernorm_bwd(dhs, sv["xt"], self.norm1.weight, VIT_EPS, dx, g, b_, rows=B * T * (N + 1), map_mode=hip.MAP_FRAME_TOKENS,
                                      map_p0=T, map_p1=N, emit=dict(mode=hip.EMIT_SKIP_CLS, rows=B * N * T, dtype=dt, T=T, N=N, scale=sv["drop_t"], group=T,
                                                                    colsum_pre=tr.bias_grad(self.temporal_fc.bias)))
@@ -627,7 +604,7 @@ class Block(nn.Module):
         dh = tr.dgrad(dqkv, self._wt("t_qkv", ta.qkv, dt))
         g, b_ = tr.grad_buffer(self.temporal_norm1.weight, zero=True)[0], tr.grad_buffer(self.temporal_norm1.bias, zero=True)[0]
         dz_prev = None
-        if fuse and emit_for is not None:  # ... and the temporal norm's backward emits the previous block's MLP operand (its drop_m, all rows incl. CLS)
+        if emit_for is not None:  # ... and the temporal norm's backward emits the previous block's MLP operand (its drop_m, all rows incl. CLS)
             _, dz_prev = hip.layernorm_bwd(dh, sv["x"], self.temporal_norm1.weight, VIT_EPS, dx, g, b_, rows=B * N * T, map_mode=hip.MAP_SKIP_CLS,
                                            map_p0=N * T, emit=dict(mode=hip.EMIT_ROWS, rows=B * S, dtype=dt, T=T, N=N, scale=emit_for["drop_m"], group=S,
                                                                    extra_cls=B))
@@ -1038,13 +1015,9 @@ class _VisualRun:
         torch.mul(dout[:, 1:].unsqueeze(2).expand(B, N, T, D), 1.0 / T, out=dy[:, 1:].view(B, N, T, D))  # one broadcast pass (was mul + repeat_interleave + copy)
         dtok = torch.empty_like(dy)
         g, b_ = tr.grad_buffer(m.norm.weight, zero=True)[0], tr.grad_buffer(m.norm.bias, zero=True)[0]
-        dz = None
-        if m.blocks[-1].fuse_ln_bwd_emit:   # the final norm's backward emits the last block's MLP operand rows (its drop-path scale)
-            S_ = 1 + N * T
-            _, dz = hip.layernorm_bwd(dy.view(-1, D), self.tok, m.norm.weight, VIT_EPS, dtok, g, b_, accumulate=False,
-                                      emit=dict(mode=hip.EMIT_ROWS, rows=B * S_, dtype=self.saved[-1]["dt"], scale=self.saved[-1]["drop_m"], group=S_))
-        else:
-            hip.layernorm_bwd(dy.view(-1, D), self.tok, m.norm.weight, VIT_EPS, dtok, g, b_, accumulate=False)
+        S_ = 1 + N * T   # the final norm's backward emits the last block's MLP operand rows (its drop-path scale)
+        _, dz = hip.layernorm_bwd(dy.view(-1, D), self.tok, m.norm.weight, VIT_EPS, dtok, g, b_, accumulate=False,
+                                  emit=dict(mode=hip.EMIT_ROWS, rows=B * S_, dtype=self.saved[-1]["dt"], scale=self.saved[-1]["drop_m"], group=S_))
         del dy
         bank = m.blocks[0]._bank()
         dt_run = self.saved[-1]["dt"]

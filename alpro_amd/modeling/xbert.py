@@ -90,9 +90,6 @@ class BertOutput(nn.Module):
 
 
 class BertLayer(nn.Module):
-    fuse_ln_bwd_emit = os.environ.get("ALPRO_FUSE_LN_BWD", "1") != "0"   # LayerNorm backward also emits the dropped-out operand rows of the next GEMMs
-    fuse_residual_ln = os.environ.get("ALPRO_FUSE_RESIDUAL_LN", "1") != "0"   # residual adds inside the post-LayerNorms (alpro_add_layernorm_fwd); False = round-2 GEMM-epilogue form (A/B)
-
     def __init__(self, config, layer_num):
         super().__init__()
         self.config = config
@@ -168,45 +165,36 @@ class BertLayer(nn.Module):
         wqkv = self._ops.get("qkv_w", (sa.query.weight, sa.key.weight, sa.value.weight), dt)
         bqkv = self._ops.get("qkv_b", (sa.query.bias, sa.key.bias, sa.value.bias), torch.float32)
         qkv = hip.gemm(h_t, wqkv, bias=bqkv)
-        cp = rt.cls_precise(dt) and self.fuse_residual_ln and self.layer_num < int(_cfg_get(self.config, "fusion_layer", 0) or 0)
+        cp = rt.cls_precise(dt) and self.layer_num < int(_cfg_get(self.config, "fusion_layer", 0) or 0)
         if cp:   # the [CLS] query once more in fp32, inside the same attention launch
             hc = h32.view(B, L, -1)[:, 0]
             ctx, lse, ctx_c = hip.attn(qkv, B, L, H, scale, key_bias, want_lse=True, drop_p=ap, drop_seed=seed_a, cls_q=self._cls_qkv(hc), cls_group=1)
         else:
             ctx, lse = hip.attn(qkv, B, L, H, scale, key_bias, want_lse=True, drop_p=ap, drop_seed=seed_a)
         ctx_full, M_full = ctx, h_t.shape[0]
-        if rows is not None and (cp or not self.fuse_residual_ln):
-            raise RuntimeError("BertLayer: an output row subset is supported on the fused residual + LayerNorm path of the fusion layers only")
+        if rows is not None and cp:
+            raise RuntimeError("BertLayer: an output row subset is supported on the fusion layers only")
         if rows is not None:
             ctx = ctx.index_select(0, rows)
             h32 = h32.index_select(0, rows)
         u, u_tiled = tr.gelu_save_buffer(ctx.shape[0], self.intermediate.dense.out_features, h_t.shape[1], dt, h_t.device) if save else (None, False)
-        if self.fuse_residual_ln:
-            # the two dense Linears write their (dropped-out) 16-bit output only; residual add + post-LayerNorm are one streaming kernel
-            # (alpro_add_layernorm_fwd), which also leaves the pre-LayerNorm sums s1 / s2 the backward needs (training only)
-            d1 = hip.gemm(ctx, self._ops.get("ao_w", so.dense.weight, dt), bias=so.dense.bias, drop_p=hp, drop_seed=seed1)
-            a_t, a32, s1 = hip.add_layernorm(h32, d1, so.LayerNorm.weight, so.LayerNorm.bias, eps, out32=True, want_x=save)
-            it = hip.gemm(a_t, self._ops.get("i_w", self.intermediate.dense.weight, dt), bias=self.intermediate.dense.bias, act=(hip.ACT_GELU_SAVE_GRAD if (save and tr.SAVE_GELU_GRAD) else hip.ACT_GELU), pre_act=u, c2_tiled=u_tiled)
-            d2 = hip.gemm(it, self._ops.get("o_w", self.output.dense.weight, dt), bias=self.output.dense.bias, drop_p=hp, drop_seed=seed2)
-            o_t, o32, s2 = hip.add_layernorm(a32, d2, self.output.LayerNorm.weight, self.output.LayerNorm.bias, eps, out32=True, want_x=save)
-            if cp:
-                D = h32.shape[1]
-                s1_c, a32_c, s2_c, o32_c = self._cls_chain(hc, ctx_c, d1, d2, B, L, hp if seed1 else 0.0)
-                o32.view(B, L, D)[:, 0] = o32_c
-                o_t.view(B, L, D)[:, 0].copy_(o32_c)          # (copy_ converts: one launch instead of .to() + copy)
-                a_t.view(B, L, D)[:, 0].copy_(a32_c)          # (the FFN's saved input row, for its weight gradient)
-                if save:                                     # the two LayerNorm backward inputs
-                    s1.view(B, L, D)[:, 0] = s1_c
-                    s2.view(B, L, D)[:, 0] = s2_c
-        else:
-            s1 = hip.gemm(ctx, self._ops.get("ao_w", so.dense.weight, dt), bias=so.dense.bias, out_dtype=torch.float32, residual=h32,
-                          drop_p=hp, drop_seed=seed1)
-            a_t, a32 = hip.layernorm(s1, so.LayerNorm.weight, so.LayerNorm.bias, eps, dt, out32=True)
-            it = hip.gemm(a_t, self._ops.get("i_w", self.intermediate.dense.weight, dt), bias=self.intermediate.dense.bias, act=(hip.ACT_GELU_SAVE_GRAD if (save and tr.SAVE_GELU_GRAD) else hip.ACT_GELU), pre_act=u, c2_tiled=u_tiled)
-            s2 = hip.gemm(it, self._ops.get("o_w", self.output.dense.weight, dt), bias=self.output.dense.bias, out_dtype=torch.float32, residual=a32,
-                          drop_p=hp, drop_seed=seed2)
-            o_t, o32 = hip.layernorm(s2, self.output.LayerNorm.weight, self.output.LayerNorm.bias, eps, dt, out32=True)
-        sv = dict(h_t=h_t, qkv=qkv, ctx=ctx, lse=lse, s1=s1, a_t=a_t, u=u, u_grad=tr.SAVE_GELU_GRAD, u_tiled=u_tiled, it=it, s2=s2, kb=key_bias, dims=(B, L, H, scale), dt=dt,
+        # the two dense Linears write their (dropped-out) 16-bit output only; residual add + post-LayerNorm are one streaming kernel
+        # (alpro_add_layernorm_fwd), which also leaves the pre-LayerNorm sums s1 / s2 the backward needs (training only)
+        d1 = hip.gemm(ctx, self._ops.get("ao_w", so.dense.weight, dt), bias=so.dense.bias, drop_p=hp, drop_seed=seed1)
+        a_t, a32, s1 = hip.add_layernorm(h32, d1, so.LayerNorm.weight, so.LayerNorm.bias, eps, out32=True, want_x=save)
+        it = hip.gemm(a_t, self._ops.get("i_w", self.intermediate.dense.weight, dt), bias=self.intermediate.dense.bias, act=hip.ACT_GELU_SAVE_GRAD if save else hip.ACT_GELU, pre_act=u, c2_tiled=u_tiled)
+        d2 = hip.gemm(it, self._ops.get("o_w", self.output.dense.weight, dt), bias=self.output.dense.bias, drop_p=hp, drop_seed=seed2)
+        o_t, o32, s2 = hip.add_layernorm(a32, d2, self.output.LayerNorm.weight, self.output.LayerNorm.bias, eps, out32=True, want_x=save)
+        if cp:
+            D = h32.shape[1]
+            s1_c, a32_c, s2_c, o32_c = self._cls_chain(hc, ctx_c, d1, d2, B, L, hp if seed1 else 0.0)
+            o32.view(B, L, D)[:, 0] = o32_c
+            o_t.view(B, L, D)[:, 0].copy_(o32_c)          # (copy_ converts: one launch instead of .to() + copy)
+            a_t.view(B, L, D)[:, 0].copy_(a32_c)          # (the FFN's saved input row, for its weight gradient)
+            if save:                                     # the two LayerNorm backward inputs
+                s1.view(B, L, D)[:, 0] = s1_c
+                s2.view(B, L, D)[:, 0] = s2_c
+        sv = dict(h_t=h_t, qkv=qkv, ctx=ctx, lse=lse, s1=s1, a_t=a_t, u=u, u_tiled=u_tiled, it=it, s2=s2, kb=key_bias, dims=(B, L, H, scale), dt=dt,
                   drop=(hp, seed1, seed2, ap, seed_a), rows=rows, ctx_full=ctx_full, M_full=M_full) if save else None
         return o32, o_t, sv
 
@@ -226,17 +214,14 @@ class BertLayer(nn.Module):
                 dy_t, dy32 = dy32, None
             dx = torch.empty((M, D), dtype=torch.float32, device=dev)
             g, b_ = tr.grad_buffer(ln.weight, zero=True)[0], tr.grad_buffer(ln.bias, zero=True)[0]
-            if self.fuse_ln_bwd_emit:
-                _, dx_t = hip.layernorm_bwd(dy_t, x, ln.weight, eps, dx, g, b_, dy2=dy32, accumulate=False,
-                                            emit=dict(mode=hip.EMIT_ROWS, rows=M, dtype=dt, drop_p=hp if drop_seed else 0.0, drop_seed=drop_seed))
-                return dx, dx_t
-            hip.layernorm_bwd(dy_t, x, ln.weight, eps, dx, g, b_, dy2=dy32, accumulate=False)
-            return dx, hip.gather_cast(dx, dt, drop_p=hp, drop_seed=drop_seed)
+            _, dx_t = hip.layernorm_bwd(dy_t, x, ln.weight, eps, dx, g, b_, dy2=dy32, accumulate=False,
+                                        emit=dict(mode=hip.EMIT_ROWS, rows=M, dtype=dt, drop_p=hp if drop_seed else 0.0, drop_seed=drop_seed))
+            return dx, dx_t
 
         hp, seed1, seed2, ap, seed_a = sv["drop"]
         ds2, ds2_t = ln_bwd(self.output.LayerNorm, sv["s2"], do_t, do32, seed2)   # ds2 is also d(a32): identity residual; ds2_t: through the FFN-output dropout
         tr.wgrad(ds2_t, sv["it"], self.output.dense.weight, self.output.dense.bias)
-        du = tr.dgrad(ds2_t, tr.transposed_operand(self._ops, "o_w^T", self.output.dense.weight, dt), gelu_pre=sv["u"], gelu_saved_grad=sv.get("u_grad", False), gelu_tiled=sv.get("u_tiled", False))
+        du = tr.dgrad(ds2_t, tr.transposed_operand(self._ops, "o_w^T", self.output.dense.weight, dt), gelu_grad=sv["u"], gelu_tiled=sv["u_tiled"])
         tr.wgrad(du, sv["a_t"], self.intermediate.dense.weight, self.intermediate.dense.bias)
         da_t = tr.dgrad(du, tr.transposed_operand(self._ops, "i_w^T", self.intermediate.dense.weight, dt))
         ds1, ds1_t = ln_bwd(so.LayerNorm, sv["s1"], da_t, ds2, seed1)       # ds1 is also d(h32): identity residual; ds1_t: through the attention-output dropout
