@@ -28,186 +28,6 @@ __device__ __forceinline__ void stage_tile(char* tile, const T* src, int64_t ld,
   }
 }
 
-template <typename T, int NKT, int NW, bool GROUPED>
-__global__ __launch_bounds__(NW * 64) void attn_bwd_kernel(const T* __restrict__ qkv, const T* __restrict__ out, const T* __restrict__ dout,
-                                                           const float* __restrict__ lse, T* __restrict__ dqkv, int L, int H, float scale,
-                                                           const float* __restrict__ key_bias, int Tn, int64_t total_rows, float drop_p,
-                                                           uint32_t drop_seed) {
-  typedef TileCfg<T> C;
-  constexpr int LP = NKT * 32;
-  constexpr int NT = NW * 64;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* tA = smem;                 // K, then Q
-  char* tB = smem + LP * C::RB;    // V, then dO
-  float* Bs = (float*)(smem + 2 * LP * C::RB);
-  float* Ls = Bs + LP;
-  float* Ds = Ls + LP;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int b = blockIdx.x / H, h = blockIdx.x - b * H;
-  const int64_t row0 = (int64_t)b * L;
-  const int Le = GROUPED ? (int)((total_rows - row0) < 32 ? (total_rows - row0) : 32) : L;
-  const int64_t ldq = 3 * (int64_t)H * HD, ldo = (int64_t)H * HD;
-  const T* qb = qkv + row0 * ldq + h * HD;
-  const T* ob = out + row0 * ldo + h * HD;
-  const T* dob = dout + row0 * ldo + h * HD;
-  T* db = dqkv + row0 * ldq + h * HD;
-  const float* lse_b = lse + ((int64_t)b * H + h) * L;
-  const uint32_t dth = drop_thresh24(drop_p);
-  const float dks = drop_seed ? 1.0f / (1.0f - drop_p) : 1.0f;
-  const uint64_t dbase = ((uint64_t)b * H + h) * (uint64_t)L;  // + q, then * L + key
-  for (int c = tid; c < LP; c += NT) {
-    Bs[c] = c < Le ? ((!GROUPED && key_bias) ? key_bias[(int64_t)b * L + c] : 0.f) : -INFINITY;
-    Ls[c] = c < Le ? lse_b[c] : INFINITY;
-  }
-  stage_tile<T>(tA, qb + H * HD, ldq, Le, LP, tid, NT);
-  stage_tile<T>(tB, qb + 2 * H * HD, ldq, Le, LP, tid, NT);
-  __syncthreads();
-
-  const int g = lane >> 5, ql = lane & 31;
-  const int ntile = (Le + 31) >> 5;
-  // ---------------------------------------------------------------- phase 1: dQ (lane = query)
-  for (int qt = wave; qt < ntile; qt += NW) {
-    const int q = qt * 32 + ql;
-    const int qc = q < Le ? q : Le - 1;
-    u32x4 qf[C::KS], dof[C::KS];
-    float delta = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < C::KS; ++ks) {
-      const int off = (2 * ks + g) * C::CN;
-      qf[ks] = *(const u32x4*)(qb + (int64_t)qc * ldq + off);
-      dof[ks] = *(const u32x4*)(dob + (int64_t)qc * ldo + off);
-      const u32x4 of = *(const u32x4*)(ob + (int64_t)qc * ldo + off);
-      float a[C::CN], c2[C::CN];
-      unpack_chunk<T>(dof[ks], a);
-      unpack_chunk<T>(of, c2);
-#pragma unroll
-      for (int e = 0; e < C::CN; ++e) delta += a[e] * c2[e];
-    }
-    delta += __shfl_xor(delta, 32, 64);
-    const float lse_q = Ls[q];
-    if (g == 0) Ds[q] = delta;
-    f32x16 dq[2];
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) dq[dt][r] = 0.f;
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt) {
-      if (kt < ntile) {
-        f32x16 s, dp;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s[r] = dp[r] = 0.f;
-        const int krow = kt * 32 + ql;
-#pragma unroll
-        for (int ks = 0; ks < C::KS; ++ks) {
-          const u32x4 ka = *(const u32x4*)(tA + tile_off<T>(krow, 2 * ks + g));
-          const u32x4 va = *(const u32x4*)(tB + tile_off<T>(krow, 2 * ks + g));
-          mma_chunk<T>(s, ka, qf[ks]);
-          mma_chunk<T>(dp, va, dof[ks]);
-        }
-#pragma unroll
-        for (int rq = 0; rq < 4; ++rq) {
-          const float4 bq = *(const float4*)(Bs + kt * 32 + 8 * rq + 4 * g);
-          const float bb[4] = {bq.x, bq.y, bq.z, bq.w};
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const int r = 4 * rq + e;
-            float p = expf(s[r] * scale + bb[e] - lse_q);
-            if (GROUPED && ((8 * rq + 4 * g + e) / Tn != ql / Tn)) p = 0.f;
-            float gd = dp[r];
-            if (!GROUPED && drop_seed) gd = drop_keep(drop_seed, (dbase + qc) * L + kt * 32 + 8 * rq + 4 * g + e, dth) ? gd * dks : 0.f;
-            s[r] = p * (gd - delta) * scale;  // dS^T
-          }
-        }
-#pragma unroll
-        for (int cc = 0; cc < C::CPT; ++cc) {
-          float v[C::CN];
-#pragma unroll
-          for (int e = 0; e < C::CN; ++e) v[e] = s[cc * C::CN + e];
-          const u32x4 bop = pack_chunk<T>(v);
-#pragma unroll
-          for (int dt = 0; dt < 2; ++dt) mma_chunk<T>(dq[dt], load_t_chunk<T>(tA, kt * 32, cc, lane, dt), bop);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    if (q < Le) store_row64<T>(db + (int64_t)q * ldq, dq, lane);
-  }
-  __syncthreads();
-  // ---------------------------------------------------------------- phase 2: dK, dV (lane = key)
-  stage_tile<T>(tA, qb, ldq, Le, LP, tid, NT);
-  stage_tile<T>(tB, dob, ldo, Le, LP, tid, NT);
-  __syncthreads();
-  for (int kt = wave; kt < ntile; kt += NW) {
-    const int key = kt * 32 + ql;
-    const int kc = key < Le ? key : Le - 1;
-    u32x4 kf[C::KS], vf[C::KS];
-#pragma unroll
-    for (int ks = 0; ks < C::KS; ++ks) {
-      const int off = (2 * ks + g) * C::CN;
-      kf[ks] = *(const u32x4*)(qb + (int64_t)kc * ldq + H * HD + off);
-      vf[ks] = *(const u32x4*)(qb + (int64_t)kc * ldq + 2 * H * HD + off);
-    }
-    const float kb = Bs[key];
-    f32x16 dk[2], dv[2];
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) dk[dt][r] = dv[dt][r] = 0.f;
-#pragma unroll 1
-    for (int qt = 0; qt < ntile; ++qt) {
-      f32x16 s, dp;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) s[r] = dp[r] = 0.f;
-      const int qrow = qt * 32 + ql;
-#pragma unroll
-      for (int ks = 0; ks < C::KS; ++ks) {
-        const u32x4 qa = *(const u32x4*)(tA + tile_off<T>(qrow, 2 * ks + g));
-        const u32x4 da = *(const u32x4*)(tB + tile_off<T>(qrow, 2 * ks + g));
-        mma_chunk<T>(s, qa, kf[ks]);
-        mma_chunk<T>(dp, da, vf[ks]);
-      }
-#pragma unroll
-      for (int rq = 0; rq < 4; ++rq) {
-        const float4 lq = *(const float4*)(Ls + qt * 32 + 8 * rq + 4 * g);
-        const float4 dq4 = *(const float4*)(Ds + qt * 32 + 8 * rq + 4 * g);
-        const float ll[4] = {lq.x, lq.y, lq.z, lq.w}, dd[4] = {dq4.x, dq4.y, dq4.z, dq4.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int r = 4 * rq + e;
-          float p = expf(s[r] * scale + kb - ll[e]);
-          if (GROUPED && ((8 * rq + 4 * g + e) / Tn != ql / Tn)) p = 0.f;
-          float dm = 1.0f;
-          if (!GROUPED && drop_seed) {
-            const int qq = qt * 32 + 8 * rq + 4 * g + e;
-            dm = drop_keep(drop_seed, (dbase + (qq < Le ? qq : Le - 1)) * L + key, dth) ? dks : 0.f;
-          }
-          s[r] = p * dm;                                // dropped P (feeds dV)
-          dp[r] = p * (dm * dp[r] - dd[e]) * scale;     // dS
-        }
-      }
-#pragma unroll
-      for (int cc = 0; cc < C::CPT; ++cc) {
-        float pv[C::CN], sv[C::CN];
-#pragma unroll
-        for (int e = 0; e < C::CN; ++e) {
-          pv[e] = s[cc * C::CN + e];
-          sv[e] = dp[cc * C::CN + e];
-        }
-        const u32x4 pb = pack_chunk<T>(pv), sb = pack_chunk<T>(sv);
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt) {
-          mma_chunk<T>(dv[dt], load_t_chunk<T>(tB, qt * 32, cc, lane, dt), pb);
-          mma_chunk<T>(dk[dt], load_t_chunk<T>(tA, qt * 32, cc, lane, dt), sb);
-        }
-      }
-    }
-    if (key < Le) {
-      store_row64<T>(db + (int64_t)key * ldq + H * HD, dk, lane);
-      store_row64<T>(db + (int64_t)key * ldq + 2 * H * HD, dv, lane);
-    }
-  }
-}
 
 // ================================================================================================
 // 16-bit full-attention backward, throughput form (same two phases and MFMA orientations as attn_bwd_kernel):
@@ -724,151 +544,20 @@ __global__ __launch_bounds__(512) void attn_bwd16k_kernel(const T* __restrict__ 
   }
 }
 
-// ================================================================================================
-// 16-bit temporal-attention backward: one WAVE per (32 consecutive tokens, head) unit, everything wave-private.
-// The four 4 KiB tiles K, V, Q, dO of the unit go global -> LDS by DMA (16 copies per unit, swizzled on the source side) and
-// every operand is then read from LDS; delta = rowsum(P o dP) (== rowsum(dO o O) for the recomputed P), so the saved
-// output is not read at all; dQ / dK / dV leave through the dead K / V tiles as 16-byte row stores.  No workgroup
-// barrier anywhere: 4 independent waves per workgroup, 2 workgroups per CU, units handed out grid-stride.
-template <typename T>
-__global__ __launch_bounds__(256, 2) void attn_temporal_bwd16_kernel(const T* __restrict__ qkv, const T* __restrict__ dout,
-                                                                    const float* __restrict__ lse, T* __restrict__ dqkv, int64_t rows, int Tn,
-                                                                    int H, float scale, int64_t units) {
-  static_assert(sizeof(T) == 2, "16-bit storage only");
-  constexpr int WB = 4 * 4096 + 256;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  char* base = smem + wave * WB;
-  char* tK = base;
-  char* tV = base + 4096;
-  char* tQ = base + 8192;
-  char* tD = base + 12288;
-  float* Ls = (float*)(base + 16384);  // -lse * log2(e); -inf on padded queries
-  float* Ds = Ls + 32;                  // -delta * scale
-  const uint32_t lds0 = lds_addr_of(base);
-  const char* zero = (const char*)g_bwd_zero;
-  const int64_t ldq = 3 * (int64_t)H * HD, ldo = (int64_t)H * HD;
-  const int g = lane >> 5, ql = lane & 31;
-  const float sl = scale * LOG2E;
-  const int qgrp = ql / Tn;
-  for (int64_t unit = (int64_t)blockIdx.x * 4 + wave; unit < units; unit += (int64_t)gridDim.x * 4) {
-    const int64_t chunk = unit / H;
-    const int h = (int)(unit - chunk * H);
-    const int64_t r0 = chunk * 32;
-    const int Le = (int)((rows - r0) < 32 ? (rows - r0) : 32);
-    const T* qb = qkv + r0 * ldq + h * HD;
-    const T* dob = dout + r0 * ldo + h * HD;
-    T* db = dqkv + r0 * ldq + h * HD;
-#pragma unroll
-    for (int piece = 0; piece < 4; ++piece) {
-      const int row = piece * 8 + (lane >> 3), slot = lane & 7;
-      const int ch = slot ^ ((((row >> 1) & 1) << 2) | ((row >> 2) & 3));
-      const bool ok = row < Le;
-      const T* src = qb + (int64_t)row * ldq + ch * 8;
-      dma16(ok ? (const char*)(src + H * HD) : zero, __builtin_amdgcn_readfirstlane(lds0 + piece * 1024));
-      dma16(ok ? (const char*)(src + 2 * H * HD) : zero, __builtin_amdgcn_readfirstlane(lds0 + 4096 + piece * 1024));
-      dma16(ok ? (const char*)src : zero, __builtin_amdgcn_readfirstlane(lds0 + 8192 + piece * 1024));
-      dma16(ok ? (const char*)(dob + (int64_t)row * ldo + ch * 8) : zero, __builtin_amdgcn_readfirstlane(lds0 + 12288 + piece * 1024));
-    }
-    if (lane < 32) Ls[lane] = lane < Le ? -lse[unit * 32 + lane] * LOG2E : -INFINITY;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    // ------------------------------------------------------------ phase 1: dQ (lane = query)
-    u32x4 qf[4], dof[4];
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      qf[ks] = *(const u32x4*)(tQ + tile_off<T>(ql, 2 * ks + g));
-      dof[ks] = *(const u32x4*)(tD + tile_off<T>(ql, 2 * ks + g));
-    }
-    f32x16 s, dp;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) s[r] = dp[r] = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      mma_chunk<T>(s, *(const u32x4*)(tK + tile_off<T>(ql, 2 * ks + g)), qf[ks]);
-      mma_chunk<T>(dp, *(const u32x4*)(tV + tile_off<T>(ql, 2 * ks + g)), dof[ks]);
-    }
-    const float nlq = Ls[ql];
-    float delta = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int key = (r & 3) + 8 * (r >> 2) + 4 * g;
-      const float p = (key / Tn == qgrp) ? __builtin_amdgcn_exp2f(fmaf(s[r], sl, nlq)) : 0.f;
-      s[r] = p;
-      delta = fmaf(p, dp[r], delta);
-    }
-    delta += __shfl_xor(delta, 32, 64);
-    const float nds = -delta * scale;
-    if (g == 0) Ds[ql] = nds;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) s[r] *= fmaf(dp[r], scale, nds);  // dS^T
-    f32x16 acc[2];
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[dt][r] = 0.f;
-#pragma unroll
-    for (int cc = 0; cc < 2; ++cc) {
-      float v[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) v[e] = s[cc * 8 + e];
-      const u32x4 bop = pack_chunk<T>(v);
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt) mma_chunk<T>(acc[dt], load_t_chunk<T>(tK, 0, cc, lane, dt), bop);
-    }
-    // K / V rows of this lane's key as phase-2 B operands, then the K tile is dead: dQ leaves through it
-    u32x4 kf[4], vf[4];
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      kf[ks] = *(const u32x4*)(tK + tile_off<T>(ql, 2 * ks + g));
-      vf[ks] = *(const u32x4*)(tV + tile_off<T>(ql, 2 * ks + g));
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    store_rows_via_lds<T>(tK, acc, db, ldq, 0, Le, lane);
-    // ------------------------------------------------------------ phase 2: dK, dV (lane = key)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) s[r] = dp[r] = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      mma_chunk<T>(s, *(const u32x4*)(tQ + tile_off<T>(ql, 2 * ks + g)), kf[ks]);
-      mma_chunk<T>(dp, *(const u32x4*)(tD + tile_off<T>(ql, 2 * ks + g)), vf[ks]);
-    }
-#pragma unroll
-    for (int rq = 0; rq < 4; ++rq) {
-      const float4 lq = *(const float4*)(Ls + 8 * rq + 4 * g);
-      const float4 dq4 = *(const float4*)(Ds + 8 * rq + 4 * g);
-      const float ll[4] = {lq.x, lq.y, lq.z, lq.w}, dd[4] = {dq4.x, dq4.y, dq4.z, dq4.w};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int r = 4 * rq + e;
-        const float p = ((8 * rq + 4 * g + e) / Tn == qgrp) ? __builtin_amdgcn_exp2f(fmaf(s[r], sl, ll[e])) : 0.f;
-        s[r] = p;
-        dp[r] = p * fmaf(dp[r], scale, dd[e]);
-      }
-    }
-    f32x16 dk[2], dv[2];
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) dk[dt][r] = dv[dt][r] = 0.f;
-#pragma unroll
-    for (int cc = 0; cc < 2; ++cc) {
-      float pv[8], sv[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        pv[e] = s[cc * 8 + e];
-        sv[e] = dp[cc * 8 + e];
-      }
-      const u32x4 pb = pack_chunk<T>(pv), sb = pack_chunk<T>(sv);
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt) {
-        mma_chunk<T>(dv[dt], load_t_chunk<T>(tD, 0, cc, lane, dt), pb);
-        mma_chunk<T>(dk[dt], load_t_chunk<T>(tQ, 0, cc, lane, dt), sb);
-      }
-    }
-    store_rows_via_lds<T>(tK, dk, db + H * HD, ldq, 0, Le, lane);
-    store_rows_via_lds<T>(tV, dv, db + 2 * H * HD, ldq, 0, Le, lane);
-  }
-}
+#define ALPRO_TDROP 0
+#define ALPRO_TKERNEL(name) name##_kernel
+#define ALPRO_TDROP_PARAMS
+#include "attention_bwd_temporal_kernels.hpp"
+#undef ALPRO_TDROP
+#undef ALPRO_TKERNEL
+#undef ALPRO_TDROP_PARAMS
+#define ALPRO_TDROP 1
+#define ALPRO_TKERNEL(name) name##_drop_kernel
+#define ALPRO_TDROP_PARAMS , float drop_p, uint32_t drop_seed
+#include "attention_bwd_temporal_kernels.hpp"
+#undef ALPRO_TDROP
+#undef ALPRO_TKERNEL
+#undef ALPRO_TDROP_PARAMS
 
 template <typename T, int NKT, bool HAS_BIAS, bool DROP>
 int launch_bwd16(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int batch, int L, int H, float scale,
@@ -957,31 +646,53 @@ extern "C" int alpro_attn_bwd(const void* qkv, const void* out, const void* dout
   return ALPRO_OK;
 }
 
-extern "C" int alpro_attn_temporal_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int dtype,
-                                       int64_t rows, int T, int H, float scale, void* stream) {
+extern "C" int alpro_attn_temporal_bwd_drop(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int dtype,
+                                            int64_t rows, int T, int H, float scale, float drop_p, uint32_t drop_seed, void* stream) {
   ALPRO_CHECK(qkv && out && dout && lse && dqkv && rows > 0 && H > 0, "alpro_attn_temporal_bwd: bad args");
   ALPRO_CHECK(T > 0 && T <= ALPRO_ATTN_MAX_T, "alpro_attn_temporal_bwd: num_frm=%d unsupported (1..%d = ALPRO_ATTN_MAX_T)", T, ALPRO_ATTN_MAX_T);
   ALPRO_CHECK(rows % T == 0, "alpro_attn_temporal_bwd: rows=%lld not a multiple of T=%d", (long long)rows, T);
-  if (32 % T != 0) return attn_temporal_any_bwd(qkv, out, dout, lse, dqkv, dtype, rows, T, H, scale, (hipStream_t)stream);
+  ALPRO_CHECK(drop_p >= 0.f && drop_p < 1.f, "alpro_attn_temporal_bwd: drop_p=%g out of range (dropout needs 0 <= p < 1)", (double)drop_p);
+  if (drop_p == 0.f) drop_seed = 0;   // either one 0: dropout off, the kernels of alpro_attn_temporal_bwd
+  hipStream_t st = (hipStream_t)stream;
+  if (32 % T != 0) return attn_temporal_any_bwd(qkv, out, dout, lse, dqkv, dtype, rows, T, H, scale, drop_p, drop_seed, st);
   const int64_t chunks = (rows + 31) / 32;
   if (dtype != ALPRO_F32) {
     const int64_t units = chunks * H;
     int64_t grid = (units + 3) / 4;
     if (grid > 512) grid = 512;
     const size_t lds = 4 * (4 * 4096 + 256);
-    static DeviceOnce once_bf16, once_f16;
+    static DeviceOnce once_bf16, once_f16, once_bf16_drop, once_f16_drop;
     set_lds_once(once_bf16, attn_temporal_bwd16_kernel<bf16_t>, lds);
     set_lds_once(once_f16, attn_temporal_bwd16_kernel<f16_t>, lds);
-    if (dtype == ALPRO_BF16) {
-      hipLaunchKernelGGL(attn_temporal_bwd16_kernel<bf16_t>, dim3((unsigned)grid), dim3(256), lds, (hipStream_t)stream, (const bf16_t*)qkv, (const bf16_t*)dout, lse,
+    set_lds_once(once_bf16_drop, attn_temporal_bwd16_drop_kernel<bf16_t>, lds);
+    set_lds_once(once_f16_drop, attn_temporal_bwd16_drop_kernel<f16_t>, lds);
+    if (drop_seed) {
+      if (dtype == ALPRO_BF16)
+        hipLaunchKernelGGL(attn_temporal_bwd16_drop_kernel<bf16_t>, dim3((unsigned)grid), dim3(256), lds, st, (const bf16_t*)qkv, (const bf16_t*)dout, lse, (bf16_t*)dqkv,
+                           rows, T, H, scale, units, drop_p, drop_seed);
+      else
+        hipLaunchKernelGGL(attn_temporal_bwd16_drop_kernel<f16_t>, dim3((unsigned)grid), dim3(256), lds, st, (const f16_t*)qkv, (const f16_t*)dout, lse, (f16_t*)dqkv,
+                           rows, T, H, scale, units, drop_p, drop_seed);
+    } else if (dtype == ALPRO_BF16) {
+      hipLaunchKernelGGL(attn_temporal_bwd16_kernel<bf16_t>, dim3((unsigned)grid), dim3(256), lds, st, (const bf16_t*)qkv, (const bf16_t*)dout, lse,
                          (bf16_t*)dqkv, rows, T, H, scale, units);
     } else {
-      hipLaunchKernelGGL(attn_temporal_bwd16_kernel<f16_t>, dim3((unsigned)grid), dim3(256), lds, (hipStream_t)stream, (const f16_t*)qkv, (const f16_t*)dout, lse,
+      hipLaunchKernelGGL(attn_temporal_bwd16_kernel<f16_t>, dim3((unsigned)grid), dim3(256), lds, st, (const f16_t*)qkv, (const f16_t*)dout, lse,
                          (f16_t*)dqkv, rows, T, H, scale, units);
     }
     return check_launch("alpro_attn_temporal_bwd");
   }
-  ALPRO_DISPATCH_DTYPE(dtype, T_, return (launch_bwd<T_, 1, 1, true>(qkv, out, dout, lse, dqkv, chunks, 32, H, scale, nullptr, T, rows, 0.f, 0u, (hipStream_t)stream)));
+  if (drop_seed) {   // fp32 is the one dtype that gets here
+    const size_t lds = 2 * 32 * (size_t)TileCfg<float>::RB + 3 * 32 * sizeof(float);
+    hipLaunchKernelGGL((attn_bwd_drop_kernel<float, 1, 1, true>), dim3((unsigned)(chunks * H)), dim3(64), lds, st, (const float*)qkv, (const float*)out, (const float*)dout, lse,
+                       (float*)dqkv, 32, H, scale, (const float*)nullptr, T, rows, drop_p, drop_seed);
+    return check_launch("alpro_attn_temporal_bwd");
+  }
+  ALPRO_DISPATCH_DTYPE(dtype, T_, return (launch_bwd<T_, 1, 1, true>(qkv, out, dout, lse, dqkv, chunks, 32, H, scale, nullptr, T, rows, 0.f, 0u, st)));
   return ALPRO_OK;
 }
 
+extern "C" int alpro_attn_temporal_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int dtype,
+                                       int64_t rows, int T, int H, float scale, void* stream) {
+  return alpro_attn_temporal_bwd_drop(qkv, out, dout, lse, dqkv, dtype, rows, T, H, scale, 0.f, 0u, stream);
+}

@@ -74,6 +74,19 @@ template <typename T> __device__ __forceinline__ u32x4 load_t_chunk16(const char
 template <> __device__ __forceinline__ u32x4 load_t_chunk<bf16_t>(const char* tile, int row0, int cc, int lane, int dt) { return load_t_chunk16<bf16_t>(tile, row0, cc, lane, dt); }
 template <> __device__ __forceinline__ u32x4 load_t_chunk<f16_t>(const char* tile, int row0, int cc, int lane, int dt) { return load_t_chunk16<f16_t>(tile, row0, cc, lane, dt); }
 
+// ---- dropout mask indices of the block-diagonal temporal kernels (32 % Tn == 0: a 32-row unit holds whole frame groups) ------------------------
+// Contract of alpro_attn_fwd with batch = rows / Tn, L = Tn: index ((grp H + h) Tn + q) Tn + k, grp = row / Tn, formed in 64 bits.  For the unit at
+// row r0 and the token of lane ql:  as a QUERY against local key `key`:  temporal_drop_base(...) + key;  as a KEY against local query `qq`:
+// temporal_drop_base_key(...) + qq * Tn.  Tokens of other groups get an index that means nothing -- their probability is 0.
+__device__ __forceinline__ uint64_t temporal_drop_base(int64_t r0, int ql, int Tn, int H, int h) {
+  const int lg = ql / Tn;
+  return (((uint64_t)(r0 / Tn + lg) * H + h) * Tn + (uint64_t)(ql - lg * Tn)) * Tn - (uint64_t)(lg * Tn);
+}
+__device__ __forceinline__ uint64_t temporal_drop_base_key(int64_t r0, int ql, int Tn, int H, int h) {
+  const int lg = ql / Tn;
+  return (((uint64_t)(r0 / Tn + lg) * H + h) * Tn - (uint64_t)(lg * Tn)) * Tn + (uint64_t)(ql - lg * Tn);
+}
+
 // ---- accumulators -> global ----------------------------------------------------------------------------------------------------------------
 // store 4 consecutive values d0..d0+3 of one row
 template <typename T> __device__ __forceinline__ void store_quad(T* dst, const float* v) {

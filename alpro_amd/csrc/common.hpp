@@ -227,6 +227,17 @@ __device__ __forceinline__ bool drop_keep(uint32_t seed, uint64_t idx, uint32_t 
   const uint32_t h = mix32(seed ^ ((uint32_t)idx * 0x9E3779B1u) ^ ((uint32_t)(idx >> 32) * 0x85EBCA77u));
   return (h >> 8) >= thresh24;
 }
+// drop_keep(seed, base + k, thresh24) for many k < 2^32 against one 64-bit base: the base as its low word and the hash terms of its high word
+// without and with the carry of the addition -- per element one 32-bit add, one multiply and a select instead of a 64-bit add and two multiplies
+struct DropBase { uint32_t lo, h0, h1; };
+__device__ __forceinline__ DropBase drop_base(uint64_t base) {
+  const uint32_t hi = (uint32_t)(base >> 32);
+  return DropBase{(uint32_t)base, hi * 0x85EBCA77u, (hi + 1u) * 0x85EBCA77u};
+}
+__device__ __forceinline__ bool drop_keep(uint32_t seed, const DropBase& b, uint32_t k, uint32_t thresh24) {
+  const uint32_t lo = b.lo + k;
+  return (mix32(seed ^ (lo * 0x9E3779B1u) ^ (lo < b.lo ? b.h1 : b.h0)) >> 8) >= thresh24;
+}
 __host__ __device__ inline uint32_t drop_thresh24(float p) { return (uint32_t)(p * 16777216.0f + 0.5f); }
 
 // ---- global -> LDS DMA issued from inline asm ---------------------------------------------------------------
@@ -265,9 +276,10 @@ int attn_long_fwd(const void* qkv, void* out, int dtype, int batch, int L, int H
 int attn_long_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int dtype, int batch, int L, int H, float scale,
                   const float* key_bias, float drop_p, uint32_t drop_seed, hipStream_t st);
 // Temporal attention over a frame count that does not divide 32 (attention_temporal_any.hip): what alpro_attn_temporal_fwd / _bwd launch there.
-int attn_temporal_any_fwd(const void* qkv, void* out, int dtype, int64_t rows, int T, int H, float scale, float* lse, hipStream_t st);
+int attn_temporal_any_fwd(const void* qkv, void* out, int dtype, int64_t rows, int T, int H, float scale, float* lse, float drop_p, uint32_t drop_seed,
+                          hipStream_t st);
 int attn_temporal_any_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int dtype, int64_t rows, int T, int H,
-                          float scale, hipStream_t st);
+                          float scale, float drop_p, uint32_t drop_seed, hipStream_t st);
 
 // Tuning knobs (measurement aids, not part of the arithmetic): initialised ONCE from the environment when the library is
 // loaded (ALPRO_GEMM_TILE / ALPRO_GEMM_GRID / ALPRO_GEMM_TUNE / ALPRO_TN_SPLITS), changed at run time only through

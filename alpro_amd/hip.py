@@ -26,7 +26,7 @@ EXPORTS = ["alpro_hip_last_error", "alpro_hip_abi_version", "alpro_hip_set_optio
            "alpro_vit_final_pool", "alpro_bert_embed_fwd", "alpro_cast_from_f32", "alpro_attn_bwd", "alpro_attn_temporal_bwd",
            "alpro_layernorm_bwd", "alpro_transpose", "alpro_transpose_batch", "alpro_gelu_bwd", "alpro_cls_mean_bwd", "alpro_scatter_add_rows", "alpro_gather_cast", "alpro_sumsq", "alpro_adamw_step", "alpro_gemm_tn_acc", "alpro_gemm_tn_acc_ws", "alpro_gemm_tn_workspace_bytes", "alpro_gemm_tn_ranges", "alpro_colsum_acc", "alpro_softmax_xent", "alpro_vtc_loss_fwd", "alpro_vtc_loss_bwd", "alpro_prepare_clips", "alpro_loss_scale_update", "alpro_add_layernorm_fwd", "alpro_layernorm_bwd_emit", "alpro_gemm_batch", "alpro_tproj_small", "alpro_attn_cls_fwd", "alpro_gemm_rows_f32", "alpro_gather_seq_fwd", "alpro_gather_seq_bwd", "alpro_scatter_add_rows_ordered",
            "alpro_hip_sched_workspace_bytes", "alpro_hip_set_sched_workspace", "alpro_hip_release_stream", "alpro_gemm_qkv_tattn", "alpro_add_layernorm_pre_mlp2", "alpro_adamw_step_lp",
-           "alpro_gemm_rows_f32_relu_mask", "alpro_clip_pool", "alpro_adamw_step_groups"]
+           "alpro_gemm_rows_f32_relu_mask", "alpro_clip_pool", "alpro_adamw_step_groups", "alpro_attn_temporal_fwd_drop", "alpro_attn_temporal_bwd_drop"]
 
 
 class GemmDesc(ctypes.Structure):
@@ -98,6 +98,8 @@ def load():
     u32 = ctypes.c_uint32
     lib.alpro_attn_bwd.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, f32, u32, vp]
     lib.alpro_attn_temporal_bwd.argtypes = [vp, vp, vp, vp, vp, i32, i64, i32, i32, f32, vp]
+    lib.alpro_attn_temporal_fwd_drop.argtypes = [vp, vp, i32, i64, i32, i32, f32, vp, f32, u32, vp]
+    lib.alpro_attn_temporal_bwd_drop.argtypes = [vp, vp, vp, vp, vp, i32, i64, i32, i32, f32, f32, u32, vp]
     lib.alpro_layernorm_bwd.argtypes = [vp, i32, i64, vp, vp, i64, vp, f32, vp, i64, i32, vp, vp, i32, i32, i32, i32, i32, f32, u32, vp, ctypes.c_size_t, vp]
     lib.alpro_layernorm_bwd_emit.argtypes = [vp, i32, i64, vp, vp, i64, vp, f32, vp, i64, i32, vp, vp, i32, i32, i32, i32, i32, f32, u32,
                                              vp, i32, i32, i32, i32, vp, i32, f32, u32, vp, i32, vp, ctypes.c_size_t, vp]
@@ -425,22 +427,33 @@ def add_layernorm_pre_mlp2(x_in, delta_t, delta_t_bias, delta_s, gamma, beta, ep
     return y
 
 
-def attn_temporal(qkv, T, H, scale, want_lse=False):
+def attn_temporal(qkv, T, H, scale, want_lse=False, drop_p=0.0, drop_seed=0):
+    """drop_p / drop_seed: dropout on the attention probabilities (alpro_attn_temporal_fwd_drop; the mask of hip.attn with batch = rows / T, L = T);
+    either one 0 = off.  The defaults make the call alpro_attn_temporal_fwd, as before."""
     lib = load()
     _dev(qkv)
     rows = qkv.shape[0]
     out = torch.empty((rows, H * 64), dtype=qkv.dtype, device=qkv.device)
     lse = torch.empty(((rows + 31) // 32, H, 32), dtype=torch.float32, device=qkv.device) if want_lse else None
-    _check(lib.alpro_attn_temporal_fwd(_ptr(qkv), _ptr(out), _CODE[qkv.dtype], rows, T, H, scale, _ptr(lse), _stream()), "alpro_attn_temporal_fwd")
+    if drop_p == 0.0 and drop_seed == 0:
+        _check(lib.alpro_attn_temporal_fwd(_ptr(qkv), _ptr(out), _CODE[qkv.dtype], rows, T, H, scale, _ptr(lse), _stream()), "alpro_attn_temporal_fwd")
+    else:
+        _check(lib.alpro_attn_temporal_fwd_drop(_ptr(qkv), _ptr(out), _CODE[qkv.dtype], rows, T, H, scale, _ptr(lse), drop_p, drop_seed, _stream()),
+               "alpro_attn_temporal_fwd_drop")
     return (out, lse) if want_lse else out
 
 
-def attn_temporal_bwd(qkv, out, dout, lse, T, H, scale):
+def attn_temporal_bwd(qkv, out, dout, lse, T, H, scale, drop_p=0.0, drop_seed=0):
+    """drop_p / drop_seed: those of the forward (the mask is regenerated from the seed)."""
     lib = load()
     _dev(qkv); _dev(out, qkv.dtype); _dev(dout, qkv.dtype); _dev(lse, torch.float32)
     dqkv = torch.empty_like(qkv)
-    _check(lib.alpro_attn_temporal_bwd(_ptr(qkv), _ptr(out), _ptr(dout), _ptr(lse), _ptr(dqkv), _CODE[qkv.dtype], qkv.shape[0], T, H, scale,
-                                       _stream()), "alpro_attn_temporal_bwd")
+    if drop_p == 0.0 and drop_seed == 0:
+        _check(lib.alpro_attn_temporal_bwd(_ptr(qkv), _ptr(out), _ptr(dout), _ptr(lse), _ptr(dqkv), _CODE[qkv.dtype], qkv.shape[0], T, H, scale,
+                                           _stream()), "alpro_attn_temporal_bwd")
+    else:
+        _check(lib.alpro_attn_temporal_bwd_drop(_ptr(qkv), _ptr(out), _ptr(dout), _ptr(lse), _ptr(dqkv), _CODE[qkv.dtype], qkv.shape[0], T, H, scale,
+                                                drop_p, drop_seed, _stream()), "alpro_attn_temporal_bwd_drop")
     return dqkv
 
 

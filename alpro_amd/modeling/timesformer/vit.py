@@ -73,13 +73,17 @@ class Attention(nn.Module):
     def __init__(self, dim, num_heads=8, qkv_bias=False, qk_scale=None, attn_drop=0., proj_drop=0., with_qkv=True):
         super().__init__()
         assert with_qkv, "the ALPRO path always uses with_qkv=True (vit.py:114,120)"
-        assert attn_drop == 0. and proj_drop == 0., "attn_drop/proj_drop are 0 in every release config"
+        assert proj_drop == 0., "proj_drop (drop_rate) must be 0: element dropout behind the projections is not implemented (attn_drop is)"
+        assert 0. <= attn_drop < 1., "attn_drop must be in [0, 1)"
         self.num_heads = num_heads
         head_dim = dim // num_heads
         assert head_dim == 64, "kernels are specialised for head_dim 64 (ViT-B/16, BERT-base)"
         self.scale = qk_scale or head_dim ** -0.5
         self.qkv = nn.Linear(dim, dim * 3, bias=qkv_bias)
         self.proj = nn.Linear(dim, dim)
+        # vit.py:79,94: dropout on the softmax probabilities, train mode only.  Parameter-free (no state_dict key); applied inside the attention
+        # kernels from a per-launch seed (Block._attn_drop_seeds), never as a module call.
+        self.attn_drop = nn.Dropout(attn_drop)
 
 
 class _ClsSide:
@@ -315,7 +319,18 @@ class Block(nn.Module):
             return pre.pop(rows)
         return self.drop_path.row_scale(rows, device)
 
-    def _forward_halves_unfused(self, x, xf, a, B, T, N, H, D, dt, drop_t=None, drop_s=None):
+    def _attn_drop_seeds(self):
+        """-> (p temporal, seed temporal, p spatial, seed spatial) of this block for this step: two draws from the dropout-seed stream in train
+        mode with attn_drop > 0 -- the reference drops whenever the module is in train mode, grad or not -- else zeros and NO draw (the stream
+        of the BERT layers is not shifted).  A seed of 0 is "off" for the kernels."""
+        pt, ps = self.temporal_attn.attn_drop.p, self.attn.attn_drop.p
+        if not self.training:
+            return 0.0, 0, 0.0, 0
+        seed_t = rt.next_dropout_seed() if pt > 0 else 0
+        seed_s = rt.next_dropout_seed() if ps > 0 else 0
+        return (pt if seed_t else 0.0), seed_t, (ps if seed_s else 0.0), seed_s
+
+    def _forward_halves_unfused(self, x, xf, a, B, T, N, H, D, dt, drop_t=None, drop_s=None, attn_p=0.0, attn_seed=0):
         """The two attention halves' tails with the unmerged temporal projection (merge_temporal_proj = False): fp32 residual
         read-modify-write in the GEMM epilogue, CLS side buffer."""
         ta, sa = self.temporal_attn, self.attn
@@ -325,7 +340,7 @@ class Block(nn.Module):
         hs = hip.layernorm(x, self.norm1.weight, self.norm1.bias, VIT_EPS, dt, rows=B * T * (N + 1),
                            map_mode=hip.MAP_FRAME_TOKENS, map_p0=T, map_p1=N)
         qkv = hip.gemm(hs, self._w("s_qkv", sa.qkv, dt), bias=sa.qkv.bias)
-        a = hip.attn(qkv, B * T, N + 1, H, sa.scale)
+        a = hip.attn(qkv, B * T, N + 1, H, sa.scale, drop_p=attn_p, drop_seed=attn_seed)
         side = torch.empty((B * T, D), dtype=torch.float32, device=x.device)
         hip.gemm(a, self._w("s_proj", sa.proj, dt), out=xf, bias=sa.proj.bias, out_dtype=torch.float32, residual=xf,
                  row_scale=drop_s, row_scale_group=N + 1,
@@ -341,6 +356,7 @@ class Block(nn.Module):
         xf = x.view(B * S, D)
         ta, sa = self.temporal_attn, self.attn
         drop_t, drop_s, drop_m = self._drop(B * N, x.device), self._drop(B * T, x.device), self._drop(B, x.device)
+        ap_t, seed_t, ap_s, seed_s = self._attn_drop_seeds()
         cp = rt.cls_precise(dt) and self.merge_temporal_proj
         side = _ClsSide.get(x.device) if (cp and rt.cls_stream(False) and x.is_cuda) else None
         if side is not None:
@@ -350,13 +366,13 @@ class Block(nn.Module):
         # ---- temporal (vit.py:146-162)
         h = hip.layernorm(x, self.temporal_norm1.weight, self.temporal_norm1.bias, VIT_EPS, dt, rows=B * N * T,
                           map_mode=hip.MAP_SKIP_CLS, map_p0=N * T)
-        if rt.fuse_temporal_attention() and hip.qkv_tattn_ok(h, T) and ta.qkv.bias is not None:
+        if rt.fuse_temporal_attention() and hip.qkv_tattn_ok(h, T) and ta.qkv.bias is not None and not seed_t:   # (the fused launch has no dropout)
             # round 6: qkv Linear + frame attention in one launch, q | k | v consumed out of the accumulators (alpro_gemm_qkv_tattn) -- the
             # (B*N*T, 2304) tensor is never written.  Forward only: forward_train keeps the two launches, whose backward needs q, k, v
             a = hip.gemm_qkv_tattn(h, self._w("t_qkv", ta.qkv, dt), ta.qkv.bias, T, H, ta.scale)
         else:
             qkv = hip.gemm(h, self._w("t_qkv", ta.qkv, dt), bias=ta.qkv.bias)
-            a = hip.attn_temporal(qkv, T, H, ta.scale)
+            a = hip.attn_temporal(qkv, T, H, ta.scale, drop_p=ap_t, drop_seed=seed_t)
         if self.merge_temporal_proj:
             # round 3: the two N = 768 projections write 16-bit deltas in plain row order; residual add + row maps + LayerNorm are one
             # streaming kernel each (alpro_add_layernorm_fwd) -- see the kernel's header comment in csrc/core.hip
@@ -372,19 +388,19 @@ class Block(nn.Module):
             qkv = hip.gemm(hs, self._w("s_qkv", sa.qkv, dt), bias=sa.qkv.bias)
             if side is not None:
                 torch.cuda.current_stream().wait_event(side.ev_q)
-                a, o_c = hip.attn(qkv, B * T, N + 1, H, sa.scale, cls_q=cls_q, cls_group=T, cls_out=o_c_buf)
+                a, o_c = hip.attn(qkv, B * T, N + 1, H, sa.scale, cls_q=cls_q, cls_group=T, cls_out=o_c_buf, drop_p=ap_s, drop_seed=seed_s)
                 ev_attn = torch.cuda.current_stream().record_event()
             elif cp:   # the CLS query of every frame once more in fp32, inside the same attention launch
-                a, o_c = hip.attn(qkv, B * T, N + 1, H, sa.scale, cls_q=self._cls_qkv(x_cls_in), cls_group=T)
+                a, o_c = hip.attn(qkv, B * T, N + 1, H, sa.scale, cls_q=self._cls_qkv(x_cls_in), cls_group=T, drop_p=ap_s, drop_seed=seed_s)
             else:
-                a = hip.attn(qkv, B * T, N + 1, H, sa.scale)
+                a = hip.attn(qkv, B * T, N + 1, H, sa.scale, drop_p=ap_s, drop_seed=seed_s)
             d_s = hip.gemm(a, self._w("s_proj", sa.proj, dt), bias=sa.proj.bias, row_scale=drop_s, row_scale_group=N + 1)
             if defer:
                 h2 = hip.add_layernorm_pre_mlp2(x, d_t, self.temporal_fc.bias, d_s, self.norm2.weight, self.norm2.bias, VIT_EPS, T, N, x_out=x)
             else:
                 h2, _ = hip.add_layernorm(x, d_s, self.norm2.weight, self.norm2.bias, VIT_EPS, mode=hip.ADD_PRE_MLP, x_out=x, T=T, N=N)
         else:
-            self._forward_halves_unfused(x, xf, a, B, T, N, H, D, dt, drop_t, drop_s)
+            self._forward_halves_unfused(x, xf, a, B, T, N, H, D, dt, drop_t, drop_s, attn_p=ap_s, attn_seed=seed_s)
             h2 = hip.layernorm(x, self.norm2.weight, self.norm2.bias, VIT_EPS, dt)
         f1 = hip.gemm(h2, self._w("fc1", self.mlp.fc1, dt), bias=self.mlp.fc1.bias, act=hip.ACT_GELU)
         hip.gemm(f1, self._w("fc2", self.mlp.fc2, dt), out=xf, bias=self.mlp.fc2.bias, out_dtype=torch.float32, residual=xf,
@@ -407,18 +423,19 @@ class Block(nn.Module):
         dev = x.device
         sv = {"x": x, "dims": (B, T, N, S, D, H), "dt": dt}
         sv["drop_t"], sv["drop_s"], sv["drop_m"] = self._drop(B * N, dev), self._drop(B * T, dev), self._drop(B, dev)
+        ap_t, seed_t, ap_s, seed_s = sv["attn_drop"] = self._attn_drop_seeds()   # the backward regenerates the masks from these
         cside = None
         if rt.cls_precise(dt) and rt.cls_stream(True) and x.is_cuda and self.merge_temporal_proj:
             cside = _ClsSide.get(dev)
             x_cls_in, cls_q, o_c_buf = self._cls_side_begin(cside, x, B, T, snapshot=False)
         h = hip.layernorm(x, self.temporal_norm1.weight, self.temporal_norm1.bias, VIT_EPS, dt, rows=B * N * T,
                           map_mode=hip.MAP_SKIP_CLS, map_p0=N * T)
-        if rt.fuse_temporal_attention(training=True) and hip.qkv_tattn_ok(h, T) and ta.qkv.bias is not None:
+        if rt.fuse_temporal_attention(training=True) and hip.qkv_tattn_ok(h, T) and ta.qkv.bias is not None and not seed_t:   # (the fused launch has no dropout)
             # round 6 (ALPRO_FUSE_TATTN=1; off by default: alpro_amd/config.py): one launch; q | k | v are still written (the backward reads them), what goes away is the attention launch and its re-read
             a_t, qkv_t, lse_t = hip.gemm_qkv_tattn(h, self._w("t_qkv", ta.qkv, dt), ta.qkv.bias, T, H, ta.scale, want_qkv=True)
         else:
             qkv_t = hip.gemm(h, self._w("t_qkv", ta.qkv, dt), bias=ta.qkv.bias)
-            a_t, lse_t = hip.attn_temporal(qkv_t, T, H, ta.scale, want_lse=True)
+            a_t, lse_t = hip.attn_temporal(qkv_t, T, H, ta.scale, want_lse=True, drop_p=ap_t, drop_seed=seed_t)
         sv["merged"] = self.merge_temporal_proj
         if self.merge_temporal_proj:
             pr = None
@@ -433,11 +450,11 @@ class Block(nn.Module):
             o_c = None
             if cside is not None:
                 torch.cuda.current_stream().wait_event(cside.ev_q)
-                a_s, lse_s, o_c = hip.attn(qkv_s, B * T, N + 1, H, sa.scale, want_lse=True, cls_q=cls_q, cls_group=T, cls_out=o_c_buf)
+                a_s, lse_s, o_c = hip.attn(qkv_s, B * T, N + 1, H, sa.scale, want_lse=True, cls_q=cls_q, cls_group=T, cls_out=o_c_buf, drop_p=ap_s, drop_seed=seed_s)
             elif rt.cls_precise(dt):
-                a_s, lse_s, o_c = hip.attn(qkv_s, B * T, N + 1, H, sa.scale, want_lse=True, cls_q=self._cls_qkv(x[:, 0]), cls_group=T)
+                a_s, lse_s, o_c = hip.attn(qkv_s, B * T, N + 1, H, sa.scale, want_lse=True, cls_q=self._cls_qkv(x[:, 0]), cls_group=T, drop_p=ap_s, drop_seed=seed_s)
             else:
-                a_s, lse_s = hip.attn(qkv_s, B * T, N + 1, H, sa.scale, want_lse=True)
+                a_s, lse_s = hip.attn(qkv_s, B * T, N + 1, H, sa.scale, want_lse=True, drop_p=ap_s, drop_seed=seed_s)
             d_s = hip.gemm(a_s, self._w("s_proj", sa.proj, dt), bias=sa.proj.bias, row_scale=sv["drop_s"], row_scale_group=N + 1)
             h2, x2 = hip.add_layernorm(xt, d_s, self.norm2.weight, self.norm2.bias, VIT_EPS, mode=hip.ADD_PRE_MLP, T=T, N=N)
             del d_s
@@ -452,7 +469,7 @@ class Block(nn.Module):
             hs = hip.layernorm(xt, self.norm1.weight, self.norm1.bias, VIT_EPS, dt, rows=B * T * (N + 1),
                                map_mode=hip.MAP_FRAME_TOKENS, map_p0=T, map_p1=N)
             qkv_s = hip.gemm(hs, self._w("s_qkv", sa.qkv, dt), bias=sa.qkv.bias)
-            a_s, lse_s = hip.attn(qkv_s, B * T, N + 1, H, sa.scale, want_lse=True)
+            a_s, lse_s = hip.attn(qkv_s, B * T, N + 1, H, sa.scale, want_lse=True, drop_p=ap_s, drop_seed=seed_s)
             x2 = torch.empty_like(x)
             side = torch.empty((B * T, D), dtype=torch.float32, device=dev)
             hip.gemm(a_s, self._w("s_proj", sa.proj, dt), out=x2.view(B * S, D), bias=sa.proj.bias, out_dtype=torch.float32,
@@ -562,6 +579,7 @@ class Block(nn.Module):
         B, T, N, S, D, H = sv["dims"]
         dt = sv["dt"]
         ta, sa = self.temporal_attn, self.attn
+        ap_t, seed_t, ap_s, seed_s = sv["attn_drop"]
         # ---- MLP: out = x2 + drop_m * (fc2(gelu(fc1(LN2(x2)))))
         if dz is None:
             dz = hip.gather_cast(dx, dt, row_scale=sv["drop_m"], row_scale_group=S)
@@ -578,7 +596,7 @@ class Block(nn.Module):
         tr.wgrad(dpo, sv["a_s"], sa.proj.weight, sa.proj.bias)
         da = tr.dgrad(dpo, self._wt("s_proj", sa.proj, dt))
         del dpo
-        dqkv = hip.attn_bwd(sv["qkv_s"], sv["a_s"], da, sv["lse_s"], B * T, N + 1, H, sa.scale)
+        dqkv = hip.attn_bwd(sv["qkv_s"], sv["a_s"], da, sv["lse_s"], B * T, N + 1, H, sa.scale, drop_p=ap_s, drop_seed=seed_s)
         tr.wgrad(dqkv, sv["hs"], sa.qkv.weight, sa.qkv.bias)
         dhs = tr.dgrad(dqkv, self._wt("s_qkv", sa.qkv, dt))
         g, b_ = tr.grad_buffer(self.norm1.weight, zero=True)[0], tr.grad_buffer(self.norm1.bias, zero=True)[0]
@@ -599,7 +617,7 @@ class Block(nn.Module):
             dpp = tr.dgrad(dfo, self._wt("t_fc", self.temporal_fc, dt), row_scale=sv["drop_t"], row_scale_group=T)
             tr.wgrad(dpp, sv["a_t"], ta.proj.weight, ta.proj.bias)
             da = tr.dgrad(dpp, self._wt("t_proj", ta.proj, dt))
-        dqkv = hip.attn_temporal_bwd(sv["qkv_t"], sv["a_t"], da, sv["lse_t"], T, H, ta.scale)
+        dqkv = hip.attn_temporal_bwd(sv["qkv_t"], sv["a_t"], da, sv["lse_t"], T, H, ta.scale, drop_p=ap_t, drop_seed=seed_t)
         tr.wgrad(dqkv, sv["h"], ta.qkv.weight, ta.qkv.bias)
         dh = tr.dgrad(dqkv, self._wt("t_qkv", ta.qkv, dt))
         g, b_ = tr.grad_buffer(self.temporal_norm1.weight, zero=True)[0], tr.grad_buffer(self.temporal_norm1.bias, zero=True)[0]
@@ -778,7 +796,7 @@ class VisionTransformer(nn.Module):
                  hybrid_backbone=None, norm_layer=nn.LayerNorm, num_frames=8, attention_type='divided_space_time', dropout=0.,
                  cross_attention_config=None, use_grad_checkpointing=False):
         super().__init__()
-        assert drop_rate == 0., "drop_rate is 0 in every release config (pos_drop/time_drop are identities)"
+        assert drop_rate == 0., "drop_rate must be 0 (pos / time / proj / MLP dropout is not implemented; attn_drop_rate is)"
         self.attention_type = attention_type
         self.depth = depth
         self.num_classes = num_classes

@@ -214,6 +214,12 @@ int alpro_add_layernorm_pre_mlp2(const float* x_in, const void* delta_t, const f
 #define ALPRO_ATTN_MAX_T 128
 int alpro_attn_temporal_fwd(const void* qkv, void* out, int dtype, int64_t rows, int T, int H, float scale,
                             float* lse /* optional (ceil(rows/32), H, 32) row log-sum-exp for the backward */, void* stream);
+/* The same with dropout on the attention probabilities (vit.py:79,94: Attention.attn_drop on the temporal half).  The mask contract is
+ * alpro_attn_fwd's with batch = rows / T and L = T: keep iff drop_keep(drop_seed, ((g*H + h)*T + q)*T + k) with g = row / T and q, k the positions
+ * inside the frame group (index formed in 64 bits); kept probabilities are scaled by 1 / (1 - drop_p); lse is that of the un-dropped row.
+ * drop_p == 0 or drop_seed == 0: off -- the kernels of alpro_attn_temporal_fwd, bit for bit.  drop_p < 0 or drop_p >= 1 is refused. */
+int alpro_attn_temporal_fwd_drop(const void* qkv, void* out, int dtype, int64_t rows, int T, int H, float scale, float* lse, float drop_p,
+                                 uint32_t drop_seed, void* stream);
 
 /* Precise CLS-query attention of the 16-bit operand modes (round 4; DESIGN.md section 2, "CLS rows precise"): for every (sequence, head) of
  * the spatial half (vit.py:180 on (B*T, 1+N) tokens, query row 0 = the CLS token of :165-167) or of a text-mode BERT layer (xbert.py:299-341,
@@ -320,6 +326,10 @@ int alpro_attn_bwd(const void* qkv, const void* out, const void* dout, const flo
                    void* stream);
 int alpro_attn_temporal_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int dtype,
                             int64_t rows, int T, int H, float scale, void* stream);
+/* Backward of alpro_attn_temporal_fwd_drop (same drop_p / drop_seed: the mask is regenerated): dP = keep / (1 - p) * (dO V^T), delta from the
+ * dropped output, P recomputed from lse.  Still no atomics and no workspace; every (row, head) of dqkv is written once. */
+int alpro_attn_temporal_bwd_drop(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int dtype,
+                                 int64_t rows, int T, int H, float scale, float drop_p, uint32_t drop_seed, void* stream);
 
 /* LayerNorm backward over D == 768: dx[map(m)] (+)= dLN(dy[m] (+ dy2[m]), x[map(m)]); dgamma/dbeta are ACCUMULATED
  * into fp32 buffers.  The forward gather map becomes a scatter; a row gathered more than once (the clip's CLS row under

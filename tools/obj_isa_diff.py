@@ -2,11 +2,17 @@
 """Compare the gfx950 code of the same translation units in two build trees, kernel by kernel: the check for a refactor that must not change
 machine code.
 
-    python tools/obj_isa_diff.py OLD_OBJDIR NEW_OBJDIR attention.o attention_bwd.o ...
+    python tools/obj_isa_diff.py [--ignore-addresses] OLD_OBJDIR NEW_OBJDIR attention.o attention_bwd.o ...
 
 Each object's gfx950 code object is extracted (llvm-objdump --offloading); per kernel symbol it compares (a) the disassembly (llvm-objdump -d,
 addresses and encodings included) and (b) the kernel's entry of the AMDGPU metadata note (llvm-readelf --notes: register counts, LDS and private
 segment sizes, arguments).  Prints one line per object and one per differing kernel; exit status 1 on any difference.  CPU only.
+
+--ignore-addresses: for a change that ADDS kernels to a translation unit and must leave the others as they are.  New kernels move the old ones
+to other addresses, so the address column, the zero fill behind a function and the distance literal of a pc-relative reference to a global
+(s_getpc_b64 + s_add_u32 / s_addc_u32) differ although every other instruction and encoding is the same (branch targets are printed relative to the
+function's symbol).  With the flag those three are dropped before comparing, and symbols found only in the new object are listed without counting
+as a difference.
 """
 import os
 import re
@@ -52,14 +58,33 @@ def kernels(co):
     return out
 
 
+def strip_addresses(text):
+    lines = [re.sub(r"// [0-9A-F]+: ", "// ", ln) for ln in text.split("\n")]
+    for i, ln in enumerate(lines):   # the literal of a pc-relative address of a global (s_getpc_b64, then s_add_u32 / s_addc_u32 with the distance)
+        if "s_getpc_b64" in ln:
+            for j in range(i + 1, min(i + 4, len(lines))):
+                if re.match(r"\s*s_addc?_u32 .*, 0x[0-9a-f]+\s", lines[j]):
+                    lines[j] = re.sub(r", 0x[0-9a-f]+\s.*$", ", <pc-relative distance>", lines[j])
+    lines[0] = re.sub(r"^\s*[0-9a-f]{16} ", "", lines[0])
+    while lines and (not lines[-1].strip() or lines[-1].strip() == "..." or lines[-1].strip().startswith("s_code_end")):
+        lines.pop()
+    return "\n".join(lines)
+
+
 def main():
-    old_dir, new_dir, names = sys.argv[1], sys.argv[2], sys.argv[3:]
+    args = sys.argv[1:]
+    relaxed = "--ignore-addresses" in args
+    args = [a for a in args if a != "--ignore-addresses"]
+    old_dir, new_dir, names = args[0], args[1], args[2:]
     bad = False
     with tempfile.TemporaryDirectory() as tmp:
         for n in names:
             a = kernels(code_object(os.path.join(old_dir, n), os.path.join(tmp, "old_" + n)))
             b = kernels(code_object(os.path.join(new_dir, n), os.path.join(tmp, "new_" + n)))
-            same_set = set(a) == set(b)
+            if relaxed:
+                a = {k: (strip_addresses(d), m) for k, (d, m) in a.items()}
+                b = {k: (strip_addresses(d), m) for k, (d, m) in b.items()}
+            same_set = set(a) == set(b) or (relaxed and set(a) <= set(b))
             common = sorted(set(a) & set(b))
             dis_diff = [k for k in common if a[k][0] != b[k][0]]
             meta_diff = [k for k in common if a[k][1] != b[k][1]]
