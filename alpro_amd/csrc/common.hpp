@@ -252,6 +252,14 @@ __device__ __forceinline__ void dma16(const void* src, uint32_t lds_addr) {
   asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(lds_addr) : "memory", "m0");
 #pragma clang diagnostic pop
 }
+// The same copy addressed as wave-uniform base (SGPR pair) + per-lane 32-bit byte offset: the form of the phase-scheduled GEMM kernels, whose
+// tile-dependent address part is wave-uniform.  (the same reserved-register site as dma16: m0 is listed as clobbered for the same reason)
+__device__ __forceinline__ void dma16_sbase(uint32_t voff, const char* sbase, uint32_t lds_addr) {
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"
+  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(lds_addr) : "memory", "m0");
+#pragma clang diagnostic pop
+}
 // 16-byte write-through store (sc1): the line leaves the XCD's L2 and lands memory-side.  Used for the attention outputs (read next by
 // the projection GEMM / the weight gradient): same speed as a non-temporal store for the attention kernel, ~0.3 % of the step for its
 // consumers (profiles/r2_gemm_epilogue_experiments.txt, experiment 10d); on the GEMM's own 16-bit outputs it LOSES 1.8 ms.

@@ -14,7 +14,7 @@
 //        O^T[d][i] = sum_j v[j][d] P^T[j][i]   4 x v_mfma_f32_16x16x32 (upper k half zero)   (lane = token i, registers = 4 consecutive d)
 //    per 16-token fragment row (16 / T groups, block-diagonal mask), with the softmax on 4 registers per lane in between.  The attention of a
 //    256 x 64 head tile costs 48 small MFMAs and ~350 VALU instructions per wave -- under 3 % of the tile's K loop.
-//  * K loop: the 8-phase idea of gemm_nt256q_kernel (gemm.hip) on a 3-phase K-tile: phase p = the 64 W rows of part p (q, k, v) = 4 fragment
+//  * K loop: the 8-phase idea of gemm_nt256q_kernel (gemm_nt256q_kernels.hpp) on a 3-phase K-tile: phase p = the 64 W rows of part p (q, k, v) = 4 fragment
 //    columns x 2 fragment rows x 2 k-steps = 16 MFMAs on 8 independent accumulators; LOAD segment (fragment reads + copies) -> barrier -> MFMA
 //    segment -> barrier, waves 4-7 one barrier behind waves 0-3, so the two waves of a SIMD alternate on the matrix pipe.  Two K-tile parities
 //    of {A: 8 wave-private 4 KiB row blocks, W0 / W1 / W2: 8 KiB each} = 112 KiB; refills (K-tile t, parity P; slots idle two phases after
@@ -29,30 +29,17 @@
 // Forward-only (inference): the training path keeps the separate launches, whose backward needs q, k, v.
 #include <type_traits>
 
-#include "common.hpp"
+#include "gemm_pipe.hpp"   // ROWB (128 bytes per LDS row: 64 16-bit elements of one K-tile) and the pieces shared with gemm_nt256q_kernel
 
 namespace alpro {
 namespace {
 
-constexpr int ROWB = 128;                  // bytes per LDS row: 64 16-bit elements of one K-tile
 constexpr int TM = 256, NTH = 512;         // tile rows, threads
 constexpr int A_BYTES = TM * ROWB;         // 32 KiB: 8 wave-private blocks of 32 rows
 constexpr int WP_BYTES = 64 * ROWB;        // 8 KiB: the 64 W rows of one part
 constexpr int PAR_BYTES = A_BYTES + 3 * WP_BYTES;   // 56 KiB per K-tile parity
 constexpr int OST_BYTES = 8 * 4096;        // output staging: 32 tokens x 64 d x 2 B per wave
 constexpr int LDS_BYTES = 2 * PAR_BYTES + OST_BYTES;
-
-template <typename T> struct Mfma;
-template <> struct Mfma<f16_t> {
-  static __device__ __forceinline__ f32x4 k32(const u32x4& a, const u32x4& b, const f32x4& c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
-  }
-};
-template <> struct Mfma<bf16_t> {
-  static __device__ __forceinline__ f32x4 k32(const u32x4& a, const u32x4& b, const f32x4& c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-  }
-};
 
 // Keep a value alive up to this point (no instruction).  Used behind the epilogue's small MFMAs: their A / B operands die with the instruction,
 // and the register allocator then likes to give the result the SAME registers at a shifted offset (seen in the built object:
@@ -114,24 +101,14 @@ __global__ __launch_bounds__(NTH, 2) void gemm_qkv_tattn_kernel(const TattnArgs 
     const int row = i * 8 + r8;
     const uint32_t vo = (uint32_t)(row * lda_b) + (((uint32_t)(lane & 7) ^ (uint32_t)((row >> 1) & 7)) << 4);
     const char* kbase = t.a + (int64_t)kt * ROWB;
-    const uint32_t dst = __builtin_amdgcn_readfirstlane(lds_base + par * PAR_BYTES + wave * 4096 + i * 1024);
-    // reserved-register site (deliberate; -Werror=inline-asm otherwise): global_load_lds takes its LDS address from m0; listing it as clobbered keeps the compiler from assuming a value of its own survives the statement
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(vo), "s"(kbase), "s"(dst) : "memory", "m0");
-#pragma clang diagnostic pop
+    dma16_sbase(vo, kbase, __builtin_amdgcn_readfirstlane(lds_base + par * PAR_BYTES + wave * 4096 + i * 1024));
   };
   // this wave's piece (rows 8 wave .. + 7) of W part `part` of K-tile kt -> parity par
   auto copy_w = [&](const Tile& t, int kt, int part, int par) {
     const int row = wave * 8 + r8;
     const uint32_t vo = (uint32_t)(row * ldw_b) + (((uint32_t)(lane & 7) ^ (uint32_t)((row >> 1) & 7)) << 4);
     const char* kbase = t.w + (int64_t)part * g.H * 64 * ldw_b + (int64_t)kt * ROWB;
-    const uint32_t dst = __builtin_amdgcn_readfirstlane(lds_base + par * PAR_BYTES + A_BYTES + part * WP_BYTES + wave * 1024);
-    // reserved-register site (deliberate; -Werror=inline-asm otherwise): see copy_a
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(vo), "s"(kbase), "s"(dst) : "memory", "m0");
-#pragma clang diagnostic pop
+    dma16_sbase(vo, kbase, __builtin_amdgcn_readfirstlane(lds_base + par * PAR_BYTES + A_BYTES + part * WP_BYTES + wave * 1024));
   };
 
   // fragment read offsets: lane l supplies row (l & 15) and the 8-element k group (l >> 4) of a 16 x 32 operand fragment
@@ -139,12 +116,6 @@ __global__ __launch_bounds__(NTH, 2) void gemm_qkv_tattn_kernel(const TattnArgs 
   const int frag0 = l15 * ROWB + ((kg ^ ((l15 >> 1) & 7)) << 4);
   const char* aF[2] = {smem + wave * 4096 + frag0, smem + wave * 4096 + (frag0 ^ 64)};
   const char* wF[2] = {smem + A_BYTES + frag0, smem + A_BYTES + (frag0 ^ 64)};
-
-  auto barrier = [] {
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-  };
 
   int cur_t = next_tile();
   if (cur_t < 0) return;
@@ -160,7 +131,7 @@ __global__ __launch_bounds__(NTH, 2) void gemm_qkv_tattn_kernel(const TattnArgs 
   for (int i = 0; i < 4; ++i) copy_a(cur, 1, i, 1);
   copy_w(cur, 1, 0, 1);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  barrier();
+  phase_barrier();
 
   const float sl = g.scale * 1.4426950408889634f;
   const int tsh = 31 - __builtin_clz((unsigned)g.Tn);   // Tn is a power of two <= 16 (launcher)
@@ -172,7 +143,7 @@ __global__ __launch_bounds__(NTH, 2) void gemm_qkv_tattn_kernel(const TattnArgs 
     for (int i = 0; i < 2; ++i)
 #pragma unroll
       for (int j = 0; j < 12; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (grp == 1) barrier();   // the upper group drops one barrier behind
+    if (grp == 1) phase_barrier();   // the upper group drops one barrier behind
 
     auto ktile = [&](auto par_tag, int t) __attribute__((always_inline)) {
       constexpr int P = decltype(par_tag)::value;
@@ -201,40 +172,40 @@ __global__ __launch_bounds__(NTH, 2) void gemm_qkv_tattn_kernel(const TattnArgs 
           for (int nf = 0; nf < 4; ++nf)
 #pragma unroll
             for (int mf = 0; mf < 2; ++mf)
-              acc[mf][part * 4 + nf] = transposed ? Mfma<T>::k32(fw[nf][ks], fa[mf][ks], acc[mf][part * 4 + nf])
-                                                  : Mfma<T>::k32(fa[mf][ks], fw[nf][ks], acc[mf][part * 4 + nf]);
+              acc[mf][part * 4 + nf] = transposed ? Mma16<T>::run(fw[nf][ks], fa[mf][ks], acc[mf][part * 4 + nf])
+                                                  : Mma16<T>::run(fa[mf][ks], fw[nf][ks], acc[mf][part * 4 + nf]);
         __builtin_amdgcn_s_setprio(0);
       };
       // phase 0: q
       load_a();
       load_w(0);
       copy_w(t1, k1, 1, P ^ 1);
-      barrier();
+      phase_barrier();
       mma(0, true);
-      barrier();
+      phase_barrier();
       // phase 1: k
       load_w(1);
       copy_w(t1, k1, 2, P ^ 1);
       copy_a(t2, k2, 0, P);
       copy_a(t2, k2, 1, P);
-      barrier();
+      phase_barrier();
       mma(1, true);
-      barrier();
+      phase_barrier();
       // phase 2: v
       load_w(2);
       copy_w(t2, k2, 0, P);
       copy_a(t2, k2, 2, P);
       copy_a(t2, k2, 3, P);
       asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-      barrier();
+      phase_barrier();
       mma(2, false);
-      barrier();
+      phase_barrier();
     };
     for (int t = 0; t < nk; t += 2) {
       ktile(std::integral_constant<int, 0>{}, t);
       ktile(std::integral_constant<int, 1>{}, t + 1);
     }
-    if (grp == 0) barrier();   // re-align
+    if (grp == 0) phase_barrier();   // re-align
 
     // ---- epilogue: the attention of this wave's 32 tokens x this head, out of the accumulators
     {
@@ -332,8 +303,8 @@ __global__ __launch_bounds__(NTH, 2) void gemm_qkv_tattn_kernel(const TattnArgs 
             ko[f] = pack_chunk<T>(kv);
           }
           f32x4 st = {0.f, 0.f, 0.f, 0.f};
-          st = Mfma<T>::k32(ko[0], qo[0], st);
-          st = Mfma<T>::k32(ko[1], qo[1], st);    // S^T[j = 4 kg + r][i = l15]
+          st = Mma16<T>::run(ko[0], qo[0], st);
+          st = Mma16<T>::run(ko[1], qo[1], st);    // S^T[j = 4 kg + r][i = l15]
           keep_alive(ko[0]); keep_alive(qo[0]); keep_alive(ko[1]); keep_alive(qo[1]);
           // softmax over the T keys of the query's own group, log2 domain
           float x[4], m = -INFINITY;
@@ -367,7 +338,7 @@ __global__ __launch_bounds__(NTH, 2) void gemm_qkv_tattn_kernel(const TattnArgs 
             // wait states behind it, with or without result / operand register overlap (round 6, profiles/r6_tattn_mfma_k16_finding.txt: K = 32 form 0 wrong of 589824,
             // every k16 variant ~8900); the K = 32 form is the one this chip's GEMMs run on
             const u32x4 va = mk4(vo.x, vo.y, 0u, 0u), pb = mk4(pt.x, pt.y, 0u, 0u);
-            o = Mfma<T>::k32(va, pb, o);
+            o = Mma16<T>::run(va, pb, o);
             keep_alive(va); keep_alive(pb);
             const u32x2 ow = mk2(pack2(o[0] * inv, o[1] * inv, (T*)0), pack2(o[2] * inv, o[3] * inv, (T*)0));
             const int row = mf * 16 + el15;       // 16-byte chunk 2 f + (kg >> 1) of the token's 128-byte row, XORed with the row
