@@ -2,6 +2,7 @@
 // (with the row maps of the forward gather turned into scatters), CLS-mean / final-pool / BERT-embedding
 // backward, and the GELU-gradient multiply.  All HBM-bound; 16-byte accesses wherever rows are contiguous.
 #include "common.hpp"
+#include "row768.hpp"
 #include <algorithm>
 
 namespace alpro {
@@ -58,57 +59,7 @@ __global__ __launch_bounds__(256) void transpose_batch_kernel(const alpro_transp
 }
 
 // ---- LayerNorm backward, D = 768, one wave per row ------------------------------------------------------
-constexpr int LN_D = 768;
 constexpr int LN_PART_BYTES = 3 * LN_D * (int)sizeof(float);  // one workgroup's column sums in the reduction workspace: dgamma | dbeta | colsum_pre
-
-__device__ __forceinline__ void ld12(const float* row, int lane, float (&v)[12]) {
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const float4 f = *(const float4*)(row + i * 256 + lane * 4);
-    v[4 * i] = f.x; v[4 * i + 1] = f.y; v[4 * i + 2] = f.z; v[4 * i + 3] = f.w;
-  }
-}
-// streamed-once rows (x, dy, the gradient stream): non-temporal
-__device__ __forceinline__ void ld12_nt(const float* row, int lane, float (&v)[12]) {
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const f32x4 f = __builtin_nontemporal_load((const f32x4*)(row + i * 256 + lane * 4));
-    v[4 * i] = f.x; v[4 * i + 1] = f.y; v[4 * i + 2] = f.z; v[4 * i + 3] = f.w;
-  }
-}
-template <typename T> __device__ __forceinline__ void ld12_t(const T* row, int lane, float (&v)[12]) {
-  if constexpr (sizeof(T) == 4) {
-    ld12_nt((const float*)row, lane, v);
-  } else {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      const u32x2 u = __builtin_nontemporal_load((const u32x2*)(row + i * 256 + lane * 4));
-      const uint32_t w0 = u.x, w1 = u.y;
-      v[4 * i] = to_f32(T{(uint16_t)(w0 & 0xffffu)}); v[4 * i + 1] = to_f32(T{(uint16_t)(w0 >> 16)});
-      v[4 * i + 2] = to_f32(T{(uint16_t)(w1 & 0xffffu)}); v[4 * i + 3] = to_f32(T{(uint16_t)(w1 >> 16)});
-    }
-  }
-}
-
-struct SrcRow {
-  int64_t row;
-  bool shared;  // the source row is gathered by several output rows (CLS under FRAME_TOKENS): scatter atomically
-};
-__device__ __forceinline__ SrcRow ln_src_row(int mode, int p0, int p1, int64_t m) {
-  SrcRow s;
-  s.shared = false;
-  if (mode == ALPRO_MAP_IDENTITY) { s.row = m; return s; }
-  if (mode == ALPRO_MAP_SKIP_CLS) { s.row = m + m / p0 + 1; return s; }
-  const int T = p0, N = p1;
-  const int64_t bt = m / (N + 1);
-  const int j = (int)(m - bt * (N + 1));
-  const int64_t b = bt / T;
-  const int t = (int)(bt - b * T);
-  const int64_t base = b * (1 + (int64_t)N * T);
-  s.shared = j == 0;
-  s.row = j == 0 ? base : base + 1 + (int64_t)(j - 1) * T + t;
-  return s;
-}
 
 // What the backward does NEXT with the gradient row this kernel has just finished (round 3): every LayerNorm backward of the path is
 // followed by an alpro_gather_cast that re-reads the fp32 row it wrote, scales it and casts it into the operand rows of the next
@@ -131,22 +82,6 @@ struct EmitArgs {
   int extra_cls;             // ROWS mode after a SKIP_CLS-mapped LayerNorm: also emit the B CLS rows (final since the previous kernel)
 };
 
-template <typename T>
-__device__ __forceinline__ void emit_store(T* p, int lane, const float (&v)[12], float sc) {
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    T* q = p + i * 256 + lane * 4;
-    if constexpr (sizeof(T) == 4) {
-      *(f32x4*)q = f32x4{v[4 * i] * sc, v[4 * i + 1] * sc, v[4 * i + 2] * sc, v[4 * i + 3] * sc};
-    } else {
-      u32x2 u;
-      u.x = pack2(v[4 * i] * sc, v[4 * i + 1] * sc, (T*)0);
-      u.y = pack2(v[4 * i + 2] * sc, v[4 * i + 3] * sc, (T*)0);
-      *(u32x2*)q = u;  // plain store: the wgrad / dgrad GEMMs read it next out of the Infinity Cache (like alpro_gather_cast)
-    }
-  }
-}
-
 // emit the finished gradient row `v` of token row r (see EmitArgs); cp accumulates the unscaled column sums (SKIP_CLS mode)
 template <typename T>
 __device__ __forceinline__ void emit_row(const EmitArgs& e, int64_t r, int lane, float (&v)[12], float (&cp)[12]) {
@@ -156,12 +91,9 @@ __device__ __forceinline__ void emit_row(const EmitArgs& e, int64_t r, int lane,
       const uint32_t th = drop_thresh24(e.drop_p);
       const float ks = 1.0f / (1.0f - e.drop_p);
 #pragma unroll
-      for (int i = 0; i < 12; ++i) {
-        const uint64_t idx = (uint64_t)r * LN_D + (uint64_t)((i >> 2) * 256 + lane * 4 + (i & 3));
-        v[i] = drop_keep(e.drop_seed, idx, th) ? v[i] * ks : 0.f;
-      }
+      for (int i = 0; i < 12; ++i) v[i] = row_drop_keep(e.drop_seed, r, lane, i, th) ? v[i] * ks : 0.f;
     }
-    emit_store<T>(out + r * LN_D, lane, v, e.scale ? e.scale[r / e.group] : 1.0f);
+    ln_store_scaled<T>(out + r * LN_D, lane, v, e.scale ? e.scale[r / e.group] : 1.0f);
     return;
   }
   const int Tn = e.p0, N = e.p1;
@@ -170,18 +102,18 @@ __device__ __forceinline__ void emit_row(const EmitArgs& e, int64_t r, int lane,
   if (e.mode == ALPRO_EMIT_FRAME) {
     if (k == 0) {
       const float inv = 1.0f / (float)Tn;
-      for (int t = 0; t < Tn; ++t) emit_store<T>(out + ((b * Tn + t) * (N + 1)) * LN_D, lane, v, (e.scale ? e.scale[b * Tn + t] : 1.0f) * inv);
+      for (int t = 0; t < Tn; ++t) ln_store_scaled<T>(out + ((b * Tn + t) * (N + 1)) * LN_D, lane, v, (e.scale ? e.scale[b * Tn + t] : 1.0f) * inv);
     } else {
       const int64_t n = (k - 1) / Tn;
       const int t = (int)((k - 1) - n * Tn);
-      emit_store<T>(out + ((b * Tn + t) * (N + 1) + 1 + n) * LN_D, lane, v, e.scale ? e.scale[b * Tn + t] : 1.0f);
+      ln_store_scaled<T>(out + ((b * Tn + t) * (N + 1) + 1 + n) * LN_D, lane, v, e.scale ? e.scale[b * Tn + t] : 1.0f);
     }
   } else {  // SKIP_CLS
     if (k == 0) return;
     const int64_t o = r - b - 1;
 #pragma unroll
     for (int i = 0; i < 12; ++i) cp[i] += v[i];
-    emit_store<T>(out + o * LN_D, lane, v, e.scale ? e.scale[o / e.group] : 1.0f);
+    ln_store_scaled<T>(out + o * LN_D, lane, v, e.scale ? e.scale[o / e.group] : 1.0f);
   }
 }
 
@@ -198,17 +130,17 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const T* __restrict_
   const int64_t wave = (int64_t)blockIdx.x * 4 + w;
   const int64_t nwaves = (int64_t)gridDim.x * 4;
   float g[12], ag[12], ab[12], cp[12];
-  ld12(gamma, lane, g);
+  ln_load(gamma, lane, g);
 #pragma unroll
   for (int i = 0; i < 12; ++i) ag[i] = ab[i] = cp[i] = 0.f;
   // one row: loads, statistics, dgamma / dbeta terms; fin = its input-gradient row (not stored here)
   auto row_grad = [&](int64_t m, int64_t srow, float (&fin)[12]) {
     float xv[12], d[12];
-    ld12_nt(x + srow * ldx, lane, xv);
-    ld12_t<T>(dy + m * ld_dy, lane, d);
+    ln_load_nt(x + srow * ldx, lane, xv);
+    ln_load_t<T>(dy + m * ld_dy, lane, d);
     if (dy2) {  // second gradient stream on the same LN output (fp32 copy consumed as a residual)
       float d2[12];
-      ld12_nt(dy2 + m * LN_D, lane, d2);
+      ln_load_nt(dy2 + m * LN_D, lane, d2);
 #pragma unroll
       for (int i = 0; i < 12; ++i) d[i] += d2[i];
     }
@@ -216,23 +148,14 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const T* __restrict_
       const uint32_t th = drop_thresh24(drop_p);
       const float ks = 1.0f / (1.0f - drop_p);
 #pragma unroll
-      for (int i = 0; i < 12; ++i) {
-        const uint64_t idx = (uint64_t)m * LN_D + (uint64_t)((i >> 2) * 256 + lane * 4 + (i & 3));
-        d[i] = drop_keep(drop_seed, idx, th) ? d[i] * ks : 0.f;
-      }
+      for (int i = 0; i < 12; ++i) d[i] = row_drop_keep(drop_seed, m, lane, i, th) ? d[i] * ks : 0.f;
     }
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 12; ++i) s += xv[i];
-    const float mean = wave_sum(s) * (1.0f / LN_D);
-    float qq = 0.f;
-#pragma unroll
-    for (int i = 0; i < 12; ++i) { xv[i] -= mean; qq += xv[i] * xv[i]; }
-    const float rstd = rsqrtf(wave_sum(qq) * (1.0f / LN_D) + eps);
+    float mean, rstd;
+    ln_stats(xv, eps, mean, rstd);
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int i = 0; i < 12; ++i) {
-      xv[i] *= rstd;            // xhat
+      xv[i] = (xv[i] - mean) * rstd;  // xhat
       ab[i] += d[i];
       ag[i] += d[i] * xv[i];
       d[i] *= g[i];             // dy * gamma
@@ -248,7 +171,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const T* __restrict_
     if (m >= rows) {  // cast-only rows: the CLS rows a SKIP_CLS-mapped LayerNorm does not touch (their gradient is already final)
       const int64_t r = (m - rows) * (1 + (int64_t)em.p1 * em.p0);
       float v[12];
-      ld12_nt(dx + r * ld_dx, lane, v);
+      ln_load_nt(dx + r * ld_dx, lane, v);
       emit_row<TE>(em, r, lane, v, cp);
       continue;
     }
@@ -275,7 +198,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const T* __restrict_
       } else {
         float* o = dx + src.row * ld_dx;
 #pragma unroll
-        for (int i = 0; i < 12; ++i) atomicAdd(o + (i >> 2) * 256 + lane * 4 + (i & 3), fin[i]);
+        for (int i = 0; i < 12; ++i) atomicAdd(o + row_col(lane, i), fin[i]);
       }
       continue;
     }
@@ -408,10 +331,7 @@ __global__ __launch_bounds__(NW * 64) void gather_cast_kernel(const float* __res
       const uint32_t th = drop_thresh24(drop_p);
       const float ks = 1.0f / (1.0f - drop_p);
 #pragma unroll
-      for (int i = 0; i < 12; ++i) {
-        const uint64_t idx = (uint64_t)m * LN_D + (uint64_t)((i >> 2) * 256 + lane * 4 + (i & 3));
-        v[i] = drop_keep(drop_seed, idx, th) ? v[i] * ks : 0.f;
-      }
+      for (int i = 0; i < 12; ++i) v[i] = row_drop_keep(drop_seed, m, lane, i, th) ? v[i] * ks : 0.f;
     }
 #pragma unroll
     for (int i = 0; i < 12; ++i) {
@@ -428,7 +348,7 @@ __global__ __launch_bounds__(NW * 64) void gather_cast_kernel(const float* __res
         u32x2 u;
         u.x = pack2(v[4 * i], v[4 * i + 1], (T*)0);
         u.y = pack2(v[4 * i + 2], v[4 * i + 3], (T*)0);
-        *(u32x2*)p = u;  // plain store: the wgrad / dgrad GEMMs read it next out of the Infinity Cache (see ln_store in core.hip)
+        *(u32x2*)p = u;  // ln_store<T> (row768.hpp) written out: the call changes this kernel's register numbers (profiles/r12_rowwise_isa.txt)
       }
     }
   };
@@ -441,8 +361,8 @@ __global__ __launch_bounds__(NW * 64) void gather_cast_kernel(const float* __res
     const int64_t r = src_row(m, sc);
     const int64_t r2 = has2 ? src_row(m2, sc2) : r;
     float v[12], v2[12];
-    ld12_nt(src + r * ld, lane, v);
-    ld12_nt(src + r2 * ld, lane, v2);
+    ln_load_nt(src + r * ld, lane, v);
+    ln_load_nt(src + r2 * ld, lane, v2);
     emit(m, v, sc);
     if (has2) emit(m2, v2, sc2);
   }
@@ -452,9 +372,7 @@ __global__ __launch_bounds__(NW * 64) void gather_cast_kernel(const float* __res
     const int w = threadIdx.x >> 6;
     __syncthreads();
 #pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) red[w][i * 256 + lane * 4 + e] = acc[4 * i + e];
+    for (int i = 0; i < 12; ++i) red[w][row_col(lane, i)] = acc[i];
     __syncthreads();
     for (int c = threadIdx.x; c < LN_D; c += NW * 64) {
       float t = 0.f;
@@ -512,7 +430,7 @@ __global__ __launch_bounds__(256) void scatter_add_rows_kernel(const float* __re
   float* d = dst + r * LN_D;
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
-    const float4 f = *(const float4*)(s + i * 256 + lane * 4);
+    const float4 f = *(const float4*)(s + i * 256 + lane * 4);   // (ln_load + row_col of row768.hpp here: other register counts)
     float* p = d + i * 256 + lane * 4;
     atomicAdd(p, f.x); atomicAdd(p + 1, f.y); atomicAdd(p + 2, f.z); atomicAdd(p + 3, f.w);
   }
@@ -529,17 +447,11 @@ __global__ __launch_bounds__(256) void scatter_add_mod_kernel(const float* __res
   for (int i = 0; i < 12; ++i) acc[i] = 0.f;
   for (int m = r; m < rows; m += idx_mod) {
     float v[12];
-    ld12_nt(src + (int64_t)m * LN_D, lane, v);
+    ln_load_nt(src + (int64_t)m * LN_D, lane, v);
 #pragma unroll
     for (int i = 0; i < 12; ++i) acc[i] += v[i];
   }
-  float* d = dst + (int64_t)r * LN_D;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    float4* p = (float4*)(d + i * 256 + lane * 4);
-    const float4 c = *p;
-    *p = make_float4(c.x + acc[4 * i], c.y + acc[4 * i + 1], c.z + acc[4 * i + 2], c.w + acc[4 * i + 3]);
-  }
+  ln_accum_row(dst + (int64_t)r * LN_D, lane, acc);
 }
 
 // ---- indexed scatter in a fixed order (round 5): the word-embedding table's gradient (xbert.py:203-210 backward) ---------------------------
@@ -591,17 +503,11 @@ __global__ __launch_bounds__(256) void scatter_add_runs_kernel(const float* __re
     const uint32_t kq = keys[q];
     if ((kq >> 13) != dest) break;
     float v[12];
-    ld12_nt(src + (int64_t)(kq & 8191u) * LN_D, lane, v);
+    ln_load_nt(src + (int64_t)(kq & 8191u) * LN_D, lane, v);
 #pragma unroll
     for (int i = 0; i < 12; ++i) acc[i] += v[i];
   }
-  float* d = dst + (int64_t)dest * LN_D;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    float4* p = (float4*)(d + i * 256 + lane * 4);
-    const float4 c = *p;
-    *p = make_float4(c.x + acc[4 * i], c.y + acc[4 * i + 1], c.z + acc[4 * i + 2], c.w + acc[4 * i + 3]);
-  }
+  ln_accum_row(dst + (int64_t)dest * LN_D, lane, acc);
 }
 
 // ---- small per-block terms of the merged temporal projection W_e = W_fc W_p (vit.py:157-162), all ViT blocks in one launch -------------

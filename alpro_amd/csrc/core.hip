@@ -1,198 +1,10 @@
-// Error plumbing + small memory-bound kernels (casts, patchify, CLS mean, BERT embeddings,
-// final-norm temporal pooling).  All are HBM-bound: one wave per 768-wide row, 16-byte accesses.
-#include <stdarg.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
+// Forward row kernels and their entry points: casts, clip preparation, patchify, CLS mean, the sequence gather, and every kernel that works on
+// 768-wide rows one wave at a time (LayerNorm, residual add + LayerNorm, final-norm temporal pooling, BERT embeddings; helpers: row768.hpp).
+// All are HBM-bound, 16-byte accesses.  The library's host state (errors, options, scheduler slots) is runtime.hip.
 #include "common.hpp"
+#include "row768.hpp"
 
 namespace alpro {
-
-static thread_local char g_err[512] = "";
-
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-}
-
-namespace {
-const char* const kOptNames[OPT_COUNT] = {"gemm_tile", "gemm_grid", "gemm_tune", "tn_splits", "tn_kind", "gemm_tail", "attn_bwd", "attn_order", "gemm_kind", "cu_budget", "ln_grid", "gemm_sched", "gemm_epi"};
-const char* const kOptEnv[OPT_COUNT] = {"ALPRO_GEMM_TILE", "ALPRO_GEMM_GRID", "ALPRO_GEMM_TUNE", "ALPRO_TN_SPLITS", "ALPRO_TN_KIND", "ALPRO_GEMM_TAIL", "ALPRO_ATTN_BWD", "ALPRO_ATTN_ORDER", "ALPRO_GEMM_KIND", "ALPRO_CU_BUDGET", "ALPRO_LN_GRID", "ALPRO_GEMM_SCHED", "ALPRO_GEMM_EPI"};
-int g_opts[OPT_COUNT];
-// Values that once selected ablations (gemm_tune >= 3, tn_kind 1, attn_bwd 3 / 4: measurement variants that have been removed) are
-// refused, from alpro_hip_set_option, alpro_hip_set_stream_option and the environment alike.
-bool option_allowed(int which, int value) {
-  if (which == OPT_GEMM_TUNE) return value >= 0 && value <= 2;
-  if (which == OPT_TN_KIND) return value == 0 || value == 2;   // 0: one group, 2: two-group schedule
-  if (which == OPT_ATTN_BWD) return value >= 0 && value <= 2;   // 0 two-phase, 1 best per shape, 2 key-owned
-  return value >= 0;
-}
-struct OptInit {
-  OptInit() {
-    for (int i = 0; i < OPT_COUNT; ++i) {
-      const char* e = getenv(kOptEnv[i]);
-      const int dflt = (i == OPT_GEMM_TUNE || i == OPT_GEMM_TAIL || i == OPT_ATTN_BWD || i == OPT_GEMM_KIND || i == OPT_GEMM_SCHED || i == OPT_GEMM_EPI) ? 1
-                       : i == OPT_TN_KIND ? 2   // (round 5: the two-group schedule of the weight-gradient kernel, -1.2 % on its 29.7 ms in the step: profiles/r5_tn_kind_ab.txt)
-                                          : 0;
-      g_opts[i] = e ? atoi(e) : dflt;
-      if (!option_allowed(i, g_opts[i])) {
-        fprintf(stderr, "libalpro_hip: %s=%d selected an ablation that has been removed (ignored)\n", kOptEnv[i], g_opts[i]);
-        g_opts[i] = dflt;
-      }
-    }
-  }
-} g_opt_init;
-}  // namespace
-
-int get_option(int which) { return __atomic_load_n(&g_opts[which], __ATOMIC_RELAXED); }
-
-// ---- per-stream option overrides (round 5) ---------------------------------------------------------------------------------------
-// A handful of (stream, option) -> value entries behind a spin lock: set by the owner of a stream (alpro_amd.optim while its gradient
-// exchange is in flight), read once per launch that consults the option.  An empty table (the normal case) costs one relaxed load.
-namespace {
-struct StreamOpt { hipStream_t st; int which, value; };
-constexpr int kMaxStreamOpts = 32;
-StreamOpt g_sopts[kMaxStreamOpts];
-int g_nsopts = 0;
-int g_sopt_lock = 0;
-struct SpinGuard {
-  SpinGuard() { while (__atomic_exchange_n(&g_sopt_lock, 1, __ATOMIC_ACQUIRE)) {} }
-  ~SpinGuard() { __atomic_store_n(&g_sopt_lock, 0, __ATOMIC_RELEASE); }
-};
-}  // namespace
-
-int get_stream_option(int which, hipStream_t st) {
-  if (__atomic_load_n(&g_nsopts, __ATOMIC_RELAXED) == 0) return -1;
-  SpinGuard g;
-  for (int i = 0; i < g_nsopts; ++i)
-    if (g_sopts[i].st == st && g_sopts[i].which == which) return g_sopts[i].value;
-  return -1;
-}
-
-// ---- tile-scheduler blocks (common.hpp) ---------------------------------------------------------------------------------------------
-// Who owns the memory.  Each (device, stream) that launches the persistent 8-phase GEMM needs one PAIR of counter blocks (2 x 1056 bytes).
-//   * A caller that wants the library to allocate nothing registers its own: alpro_hip_set_sched_workspace(stream, ptr, bytes).
-//   * Otherwise the first such launch on a device makes ONE hipMalloc of kSchedSlots pairs (135 KB) for that device -- the only allocation
-//     this library ever makes -- and the stream's pair is cleared by a hipMemsetAsync ON THAT STREAM (ordered before the launch; no device-wide
-//     synchronisation, round 6).
-// A slot belongs to its (device, stream) until alpro_hip_release_stream(stream): a destroyed stream's handle value may be handed out again
-// by the runtime, so owners of short-lived streams release them (the re-created stream then starts from a cleared pair instead of
-// inheriting one).  With all kSchedSlots slots taken a further stream runs the static walk (same results, no CU-theft tolerance).
-namespace {
-constexpr int kSchedSlots = 64;
-struct SchedSlot {
-  int dev;
-  hipStream_t st;
-  uint32_t* pair;   // 2 x SCHED_BLOCK_U32 dwords
-  unsigned n;       // launches committed on this pair: launch n works on block n & 1 and zeroes the other
-  int lock;
-  bool used, caller_owned;
-};
-SchedSlot g_sched[kSchedSlots];
-int g_sched_table_lock = 0;
-uint32_t* g_sched_pool[64];   // per device: kSchedSlots pairs (slot i's pair is pool + i * pair size)
-constexpr size_t kPairBytes = (size_t)2 * SCHED_BLOCK_U32 * sizeof(uint32_t);
-struct TableGuard {
-  TableGuard() { while (__atomic_exchange_n(&g_sched_table_lock, 1, __ATOMIC_ACQUIRE)) {} }
-  ~TableGuard() { __atomic_store_n(&g_sched_table_lock, 0, __ATOMIC_RELEASE); }
-};
-SchedSlot* find_slot(int dev, hipStream_t st) {
-  for (int i = 0; i < kSchedSlots; ++i)
-    if (g_sched[i].used && g_sched[i].dev == dev && g_sched[i].st == st) return &g_sched[i];
-  return nullptr;
-}
-// a free slot for (dev, st) on `pair` (nullptr: the device pool's), cleared on the stream; nullptr when the table is full / the pool cannot be made
-SchedSlot* make_slot(int dev, hipStream_t st, uint32_t* pair) {
-  int at = -1;
-  for (int i = 0; i < kSchedSlots && at < 0; ++i)
-    if (!g_sched[i].used) at = i;
-  if (at < 0) return nullptr;
-  const bool own = pair != nullptr;
-  if (!own) {
-    if (!g_sched_pool[dev]) {
-      void* pmem = nullptr;
-      if (hipMalloc(&pmem, kSchedSlots * kPairBytes) == hipSuccess) g_sched_pool[dev] = (uint32_t*)pmem;
-      else (void)hipGetLastError();
-    }
-    if (!g_sched_pool[dev]) return nullptr;
-    pair = g_sched_pool[dev] + (size_t)at * 2 * SCHED_BLOCK_U32;
-  }
-  if (hipMemsetAsync(pair, 0, kPairBytes, st) != hipSuccess) {
-    (void)hipGetLastError();
-    return nullptr;
-  }
-  SchedSlot* s = &g_sched[at];
-  s->dev = dev;
-  s->st = st;
-  s->pair = pair;
-  s->n = 0;
-  s->lock = 0;
-  s->caller_owned = own;
-  s->used = true;
-  return s;
-}
-}  // namespace
-
-SchedLaunch::SchedLaunch(hipStream_t st, bool enabled) {
-  if (!enabled) return;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return;
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) {   // a captured launch is replayed with the SAME block: static walk
-    (void)hipGetLastError();
-    return;
-  }
-  SchedSlot* s = nullptr;
-  {
-    TableGuard g;
-    s = find_slot(dev, st);
-    if (!s) s = make_slot(dev, st, nullptr);
-  }
-  if (!s) return;
-  while (__atomic_exchange_n(&s->lock, 1, __ATOMIC_ACQUIRE)) {}
-  slot = s;
-  cur = s->pair + (size_t)(s->n & 1u) * SCHED_BLOCK_U32;
-  prev = s->pair + (size_t)((s->n + 1u) & 1u) * SCHED_BLOCK_U32;
-}
-
-// The pair's parity moves on only when the launch was accepted: a launch that failed at enqueue never ran, so `cur` is still
-// clear and `prev` still holds the previous launch's counts -- exactly what the next attempt expects.
-void SchedLaunch::commit(bool launched) {
-  if (slot && launched) ++((SchedSlot*)slot)->n;
-}
-
-SchedLaunch::~SchedLaunch() {
-  if (slot) __atomic_store_n(&((SchedSlot*)slot)->lock, 0, __ATOMIC_RELEASE);
-}
-
-int sched_set_workspace(hipStream_t st, void* ptr, size_t bytes) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { set_error("alpro_hip_set_sched_workspace: no current device"); return ALPRO_ERR_INVALID; }
-  TableGuard g;
-  SchedSlot* s = find_slot(dev, st);
-  if (s) {   // (the stream's launches so far are ordered before the clear make_slot() issues on it)
-    while (__atomic_exchange_n(&s->lock, 1, __ATOMIC_ACQUIRE)) {}
-    s->used = false;
-    __atomic_store_n(&s->lock, 0, __ATOMIC_RELEASE);
-  }
-  if (!ptr) return ALPRO_OK;
-  if (bytes < kPairBytes || ((uintptr_t)ptr % 16) != 0) { set_error("alpro_hip_set_sched_workspace: needs %zu bytes, 16-byte aligned (got %zu)", kPairBytes, bytes); return ALPRO_ERR_INVALID; }
-  if (!make_slot(dev, st, (uint32_t*)ptr)) { set_error("alpro_hip_set_sched_workspace: all %d (device, stream) slots are taken: release a stream first", kSchedSlots); return ALPRO_ERR_INVALID; }
-  return ALPRO_OK;
-}
-
-int check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("%s: launch failed: %s", what, hipGetErrorString(e));
-    return ALPRO_ERR_LAUNCH;
-  }
-  return ALPRO_OK;
-}
-
 namespace {
 
 // ---- cast ------------------------------------------------------------------------------------
@@ -251,75 +63,7 @@ __global__ void cls_mean_residual_kernel(const float* __restrict__ x_in, int64_t
   }
 }
 
-// ---- row LayerNorm helpers (D = 768: 12 fp32 per lane, one wave per row) -------------------------
-constexpr int LN_D = 768, LN_V = 3;
-
-__device__ __forceinline__ void ln_load(const float* row, int lane, float (&v)[12]) {
-#pragma unroll
-  for (int i = 0; i < LN_V; ++i) {
-    const float4 f = *(const float4*)(row + i * 256 + lane * 4);
-    v[4 * i] = f.x; v[4 * i + 1] = f.y; v[4 * i + 2] = f.z; v[4 * i + 3] = f.w;
-  }
-}
-__device__ __forceinline__ void ln_load_nt(const float* row, int lane, float (&v)[12]) {  // streamed-once token rows
-#pragma unroll
-  for (int i = 0; i < LN_V; ++i) {
-    const f32x4 f = __builtin_nontemporal_load((const f32x4*)(row + i * 256 + lane * 4));
-    v[4 * i] = f.x; v[4 * i + 1] = f.y; v[4 * i + 2] = f.z; v[4 * i + 3] = f.w;
-  }
-}
-__device__ __forceinline__ void ln_stats(const float (&v)[12], float eps, float& mean, float& rstd) {
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < 12; ++i) s += v[i];
-  mean = wave_sum(s) * (1.0f / LN_D);
-  float q = 0.f;
-#pragma unroll
-  for (int i = 0; i < 12; ++i) {
-    const float d = v[i] - mean;
-    q += d * d;
-  }
-  rstd = rsqrtf(wave_sum(q) * (1.0f / LN_D) + eps);
-}
-__device__ __forceinline__ void ln_affine(float (&v)[12], float mean, float rstd, const float* gamma, const float* beta, int lane) {
-#pragma unroll
-  for (int i = 0; i < LN_V; ++i) {
-    const float4 g = *(const float4*)(gamma + i * 256 + lane * 4), b = *(const float4*)(beta + i * 256 + lane * 4);
-    v[4 * i] = (v[4 * i] - mean) * rstd * g.x + b.x;
-    v[4 * i + 1] = (v[4 * i + 1] - mean) * rstd * g.y + b.y;
-    v[4 * i + 2] = (v[4 * i + 2] - mean) * rstd * g.z + b.z;
-    v[4 * i + 3] = (v[4 * i + 3] - mean) * rstd * g.w + b.w;
-  }
-}
-template <typename T>
-__device__ __forceinline__ void ln_store(T* row, int lane, const float (&v)[12]) {
-#pragma unroll
-  for (int i = 0; i < LN_V; ++i) {
-    if constexpr (sizeof(T) == 4) {
-      __builtin_nontemporal_store(f32x4{v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3]}, (f32x4*)(row + i * 256 + lane * 4));
-    } else {
-      T* p = row + i * 256 + lane * 4;
-      u32x2 u;
-      u.x = pack2(v[4 * i], v[4 * i + 1], (T*)0);
-      u.y = pack2(v[4 * i + 2], v[4 * i + 3], (T*)0);
-      *(u32x2*)p = u;  // plain, not non-temporal: 154 MB at the benchmark size stay in the Infinity Cache for the GEMM that reads them next
-                       // (step 174.1 -> 171.4 ms together with gather_cast; the same change on GEMM / attention outputs LOSES 5 ms)
-    }
-  }
-}
-
-__device__ __forceinline__ int64_t ln_src_row(int mode, int p0, int p1, int64_t m) {
-  if (mode == ALPRO_MAP_IDENTITY) return m;
-  if (mode == ALPRO_MAP_SKIP_CLS) return m + m / p0 + 1;
-  const int T = p0, N = p1;  // FRAME_TOKENS gather
-  const int64_t bt = m / (N + 1);
-  const int j = (int)(m - bt * (N + 1));
-  const int64_t b = bt / T;
-  const int t = (int)(bt - b * T);
-  const int64_t base = b * (1 + (int64_t)N * T);
-  return j == 0 ? base : base + 1 + (int64_t)(j - 1) * T + t;
-}
-
+// ---- row LayerNorm (D = 768, one wave per row: the row helpers are row768.hpp) ---------------------
 template <typename T>
 __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restrict__ x, int64_t ldx, const float* __restrict__ gamma,
                                                             const float* __restrict__ beta, float eps, T* __restrict__ y, int64_t ldy,
@@ -330,7 +74,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
   const int64_t nwaves = (int64_t)gridDim.x * 4;
   for (int64_t m = wave; m < rows; m += nwaves) {
     float v[12], mean, rstd;
-    ln_load_nt(x + ln_src_row(mode, p0, p1, m) * ldx, lane, v);
+    ln_load_nt(x + ln_src_row(mode, p0, p1, m).row * ldx, lane, v);
     ln_stats(v, eps, mean, rstd);
     ln_affine(v, mean, rstd, gamma, beta, lane);
     ln_store<T>(y + m * ldy, lane, v);
@@ -341,7 +85,6 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
     }
   }
 }
-
 
 // ---- the fusion encoder's input as a row gather (round 5) -----------------------------------------------------------------------
 // alpro_models.py:278-281,325-330,360-363 build the three fusion batches with torch.cat over text / video embeddings and gathers of the
@@ -396,7 +139,7 @@ __global__ __launch_bounds__(256) void gather_seq_bwd_kernel(const float* __rest
       for (int i = 0; i < 12; ++i) acc[i] += v[i];
       if (d_t) {
 #pragma unroll
-        for (int i = 0; i < LN_V; ++i) {
+        for (int i = 0; i < LN_V; ++i) {   // add_delta_row<T>'s unpack (row768.hpp) on a PLAIN load: that helper's load is non-temporal
           const u32x2 u = *(const u32x2*)(d_t + m * LN_D + i * 256 + lane * 4);
           const uint32_t ux = u.x, uy = u.y;
           acc[4 * i] += to_f32(T{(uint16_t)(ux & 0xFFFFu)});
@@ -430,24 +173,6 @@ __global__ __launch_bounds__(256) void gather_seq_bwd_kernel(const float* __rest
 // FIRST (then its bias, then the spatial delta: the order of fp32 additions of the PRE_SPATIAL + PRE_MLP pair, so x' is bit for bit the same).
 // The inference forward then runs PRE_SPATIAL with x_out = NULL: the intermediate x + temporal branch is never written (-3 KB of 9 per row there,
 // +1.5 KB here).
-template <typename T>
-__device__ __forceinline__ void add_delta_row(const T* drow, int lane, float (&v)[12], float w) {
-#pragma unroll
-  for (int i = 0; i < LN_V; ++i) {
-    if constexpr (sizeof(T) == 4) {
-      const f32x4 f = __builtin_nontemporal_load((const f32x4*)(drow + i * 256 + lane * 4));
-      v[4 * i] += w * f.x; v[4 * i + 1] += w * f.y; v[4 * i + 2] += w * f.z; v[4 * i + 3] += w * f.w;
-    } else {
-      const u32x2 u = __builtin_nontemporal_load((const u32x2*)(drow + i * 256 + lane * 4));
-      const uint32_t ux = u.x, uy = u.y;
-      v[4 * i] += w * to_f32(T{(uint16_t)(ux & 0xFFFFu)});
-      v[4 * i + 1] += w * to_f32(T{(uint16_t)(ux >> 16)});
-      v[4 * i + 2] += w * to_f32(T{(uint16_t)(uy & 0xFFFFu)});
-      v[4 * i + 3] += w * to_f32(T{(uint16_t)(uy >> 16)});
-    }
-  }
-}
-
 template <typename T, int MODE>
 __global__ __launch_bounds__(256) void add_layernorm_fwd_kernel(const float* __restrict__ x_in, const T* __restrict__ delta, const float* __restrict__ dbias,
                                                                 float* __restrict__ x_out, const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -501,7 +226,7 @@ __global__ __launch_bounds__(256) void add_layernorm_fwd_kernel(const float* __r
         add_delta_row<T>(delta2 + (r - b - 1) * LN_D, lane, v, 1.0f);
         if (dbias2) {
 #pragma unroll
-          for (int i = 0; i < LN_V; ++i) {
+          for (int i = 0; i < LN_V; ++i) {   // (v += a plain row; as a row768.hpp helper this add compiles to other code)
             const float4 f = *(const float4*)(dbias2 + i * 256 + lane * 4);
             v[4 * i] += f.x; v[4 * i + 1] += f.y; v[4 * i + 2] += f.z; v[4 * i + 3] += f.w;
           }
@@ -596,10 +321,7 @@ __global__ __launch_bounds__(256) void bert_embed_kernel(const int64_t* __restri
     const uint32_t th = drop_thresh24(drop_p);
     const float ks = 1.0f / (1.0f - drop_p);
 #pragma unroll
-    for (int i = 0; i < 12; ++i) {
-      const uint64_t idx = (uint64_t)m * LN_D + (uint64_t)((i >> 2) * 256 + lane * 4 + (i & 3));
-      v[i] = drop_keep(drop_seed, idx, th) ? v[i] * ks : 0.f;
-    }
+    for (int i = 0; i < 12; ++i) v[i] = row_drop_keep(drop_seed, m, lane, i, th) ? v[i] * ks : 0.f;
   }
   ln_store<float>(y32 + (int64_t)m * LN_D, lane, v);
   if (y_t) ln_store<T>(y_t + (int64_t)m * LN_D, lane, v);
@@ -620,82 +342,6 @@ inline int grid_for(int64_t work_items, int per_block, int cap = 256 * 16) {
 }  // namespace alpro
 
 using namespace alpro;
-
-extern "C" const char* alpro_hip_last_error(void) { return g_err; }
-extern "C" int alpro_hip_abi_version(void) { return ALPRO_HIP_ABI_VERSION; }
-extern "C" int alpro_hip_set_option(const char* name, int value) {
-  using namespace alpro;
-  for (int i = 0; name && i < OPT_COUNT; ++i)
-    if (!strcmp(name, kOptNames[i])) {
-      if (!option_allowed(i, value)) {
-        set_error("alpro_hip_set_option: %s=%d selected an ablation that has been removed; it is not a valid value", name, value);
-        return ALPRO_ERR_INVALID;
-      }
-      __atomic_store_n(&g_opts[i], value, __ATOMIC_RELAXED);
-      return ALPRO_OK;
-    }
-  set_error("alpro_hip_set_option: unknown option '%s'", name ? name : "(null)");
-  return ALPRO_ERR_INVALID;
-}
-
-extern "C" int alpro_hip_set_stream_option(void* stream, const char* name, int value) {
-  using namespace alpro;
-  int which = -1;
-  for (int i = 0; name && i < OPT_COUNT; ++i)
-    if (!strcmp(name, kOptNames[i])) which = i;
-  if (which < 0) {
-    set_error("alpro_hip_set_stream_option: unknown option '%s'", name ? name : "(null)");
-    return ALPRO_ERR_INVALID;
-  }
-  if (value >= 0 && !option_allowed(which, value)) {
-    set_error("alpro_hip_set_stream_option: %s=%d selected an ablation that has been removed; it is not a valid value", name, value);
-    return ALPRO_ERR_INVALID;
-  }
-  SpinGuard g;
-  int at = -1;
-  for (int i = 0; i < g_nsopts; ++i)
-    if (g_sopts[i].st == (hipStream_t)stream && g_sopts[i].which == which) at = i;
-  if (value < 0) {   // clear the override
-    if (at >= 0) {
-      g_sopts[at] = g_sopts[g_nsopts - 1];
-      __atomic_store_n(&g_nsopts, g_nsopts - 1, __ATOMIC_RELAXED);
-    }
-    return ALPRO_OK;
-  }
-  if (at < 0) {
-    if (g_nsopts == kMaxStreamOpts) {
-      set_error("alpro_hip_set_stream_option: more than %d (stream, option) overrides", kMaxStreamOpts);
-      return ALPRO_ERR_INVALID;
-    }
-    at = g_nsopts;
-    g_sopts[at].st = (hipStream_t)stream;
-    g_sopts[at].which = which;
-    g_sopts[at].value = value;
-    __atomic_store_n(&g_nsopts, g_nsopts + 1, __ATOMIC_RELAXED);
-  }
-  g_sopts[at].value = value;
-  return ALPRO_OK;
-}
-
-extern "C" size_t alpro_hip_sched_workspace_bytes(void) { return (size_t)2 * alpro::SCHED_BLOCK_U32 * sizeof(uint32_t); }
-
-extern "C" int alpro_hip_set_sched_workspace(void* stream, void* ptr, size_t bytes) { return alpro::sched_set_workspace((hipStream_t)stream, ptr, bytes); }
-
-extern "C" int alpro_hip_release_stream(void* stream) {
-  using namespace alpro;
-  {   // every per-stream option override of that stream
-    SpinGuard g;
-    for (int i = 0; i < g_nsopts;) {
-      if (g_sopts[i].st == (hipStream_t)stream) {
-        g_sopts[i] = g_sopts[g_nsopts - 1];
-        __atomic_store_n(&g_nsopts, g_nsopts - 1, __ATOMIC_RELAXED);
-      } else {
-        ++i;
-      }
-    }
-  }
-  return sched_set_workspace((hipStream_t)stream, nullptr, 0);   // ... and its tile-scheduler slot (a caller-owned workspace is simply forgotten)
-}
 
 extern "C" int alpro_cast_from_f32(const float* src, void* dst, int dtype, int64_t n, void* stream) {
   ALPRO_CHECK(src && dst && n >= 0, "alpro_cast_from_f32: bad args");

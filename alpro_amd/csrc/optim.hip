@@ -3,6 +3,7 @@
 // (run_pretrain_sparse.py:633) folded in.  One pass over (param, grad, m, v): 16 B/param read + 12 B/param written.
 #include "common.hpp"
 #include <algorithm>
+#include <type_traits>
 
 namespace alpro {
 namespace {
@@ -43,6 +44,29 @@ __global__ __launch_bounds__(256) void sumsq_finish_kernel(const float* __restri
   if (threadIdx.x == 0) *out += (sh[0] + sh[1]) + (sh[2] + sh[3]);
 }
 
+// ---- the pieces adamw_kernel and adamw_groups_kernel share (profiles/r12_rowwise_isa.txt: which ones, and why not the others) ----------------
+// torch.nn.utils.clip_grad_norm_ folded into the gradient coefficient: ONE coefficient from the global norm, over all parameters
+__device__ __forceinline__ float adamw_clip(float coef, const float* gnorm_sq, float max_norm) {
+  if (gnorm_sq && max_norm > 0.f) {
+    const float total = sqrtf(*gnorm_sq) * coef;
+    coef *= fminf(max_norm / (total + 1e-6f), 1.0f);
+  }
+  return coef;
+}
+
+// one whole chunk back to memory.  LP: storage type of the optional 16-bit mirror of the parameters (float = none)
+template <typename LP>
+__device__ __forceinline__ void adamw_store4(float* p, float* g, float* m, float* v, LP* lp, int zero_grad, int64_t i, const float (&pv)[4],
+                                             const float (&mv)[4], const float (&vv)[4]) {
+  *(float4*)(p + i) = make_float4(pv[0], pv[1], pv[2], pv[3]);
+  *(float4*)(m + i) = make_float4(mv[0], mv[1], mv[2], mv[3]);
+  *(float4*)(v + i) = make_float4(vv[0], vv[1], vv[2], vv[3]);
+  if (zero_grad) *(float4*)(g + i) = make_float4(0.f, 0.f, 0.f, 0.f);   // optimizer.zero_grad() folded in (round 4): no separate 0.94 GB memset
+  if constexpr (sizeof(LP) == 2) {
+    if (lp) *(u32x2*)(lp + i) = mk2(pack2(pv[0], pv[1], (LP*)0), pack2(pv[2], pv[3], (LP*)0));   // the same roundings as alpro_cast_from_f32
+  }
+}
+
 // LP: storage type of the optional 16-bit mirror of the parameters (the GEMM operands' flat copy, alpro_adamw_step_lp; float = none).
 template <typename LP>
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
@@ -68,10 +92,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float
     const float t = dyn[2] + 1.0f;
     step_size = correct_bias ? lr * sqrtf(1.0f - powf(beta2, t)) / (1.0f - powf(beta1, t)) : lr;
   }
-  if (gnorm_sq && max_norm > 0.f) {
-    const float total = sqrtf(*gnorm_sq) * coef;
-    coef *= fminf(max_norm / (total + 1e-6f), 1.0f);  // torch.nn.utils.clip_grad_norm_
-  }
+  coef = adamw_clip(coef, gnorm_sq, max_norm);
   auto update = [&](float (&pv)[4], const float (&gv)[4], float (&mv)[4], float (&vv)[4]) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -83,15 +104,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float
       if (weight_decay > 0.f) pv[k] = pv[k] - lr * weight_decay * pv[k];
     }
   };
-  auto store4 = [&](int64_t i, const float (&pv)[4], const float (&mv)[4], const float (&vv)[4]) {
-    *(float4*)(p + i) = make_float4(pv[0], pv[1], pv[2], pv[3]);
-    *(float4*)(m + i) = make_float4(mv[0], mv[1], mv[2], mv[3]);
-    *(float4*)(v + i) = make_float4(vv[0], vv[1], vv[2], vv[3]);
-    if (zero_grad) *(float4*)(g + i) = make_float4(0.f, 0.f, 0.f, 0.f);   // optimizer.zero_grad() folded in (round 4): no separate 0.94 GB memset
-    if constexpr (sizeof(LP) == 2) {
-      if (lp) *(u32x2*)(lp + i) = mk2(pack2(pv[0], pv[1], (LP*)0), pack2(pv[2], pv[3], (LP*)0));   // the same roundings as alpro_cast_from_f32
-    }
-  };
+  auto store4 = [&](int64_t i, const float (&pv)[4], const float (&mv)[4], const float (&vv)[4]) { adamw_store4<LP>(p, g, m, v, lp, zero_grad, i, pv, mv, vv); };
   // Two float4 of each array per iteration (round 6): all eight loads are issued before the first divide -- one float4 per array left the pass at
   // 5.1 TB/s with three quarters of the wave cycles stalled on memory.
   const int64_t stride = (int64_t)gridDim.x * blockDim.x * 4;
@@ -195,10 +208,7 @@ __global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p
     if (grads_scaled) coef /= dyn[0];
     dyn_t = dyn[2] + 1.0f;
   }
-  if (gnorm_sq && max_norm > 0.f) {   // ONE coefficient from the global norm: clip_grad_norm_ is over all parameters, not per group
-    const float total = sqrtf(*gnorm_sq) * coef;
-    coef *= fminf(max_norm / (total + 1e-6f), 1.0f);
-  }
+  coef = adamw_clip(coef, gnorm_sq, max_norm);
   auto update = [&](const SegHP& h, float (&pv)[4], const float (&gv)[4], float (&mv)[4], float (&vv)[4]) {
     const float lr = h.lr, beta1 = h.beta1, beta2 = h.beta2, eps = h.eps, weight_decay = h.weight_decay, step_size = h.step_size;
 #pragma unroll
@@ -211,15 +221,7 @@ __global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p
       if (weight_decay > 0.f) pv[k] = pv[k] - lr * weight_decay * pv[k];
     }
   };
-  auto store4 = [&](int64_t i, const float (&pv)[4], const float (&mv)[4], const float (&vv)[4]) {
-    *(float4*)(p + i) = make_float4(pv[0], pv[1], pv[2], pv[3]);
-    *(float4*)(m + i) = make_float4(mv[0], mv[1], mv[2], mv[3]);
-    *(float4*)(v + i) = make_float4(vv[0], vv[1], vv[2], vv[3]);
-    if (zero_grad) *(float4*)(g + i) = make_float4(0.f, 0.f, 0.f, 0.f);
-    if constexpr (sizeof(LP) == 2) {
-      if (lp) *(u32x2*)(lp + i) = mk2(pack2(pv[0], pv[1], (LP*)0), pack2(pv[2], pv[3], (LP*)0));   // the same roundings as alpro_cast_from_f32
-    }
-  };
+  auto store4 = [&](int64_t i, const float (&pv)[4], const float (&mv)[4], const float (&vv)[4]) { adamw_store4<LP>(p, g, m, v, lp, zero_grad, i, pv, mv, vv); };
   auto one_chunk = [&](int64_t q) {   // a chunk on its own, element by element where it is ragged, its segment looked up by the lane
     if (q >= n) return;
     const int cnt = (q + 4 <= n) ? 4 : (int)(n - q);
@@ -286,6 +288,23 @@ inline int grid_for(int64_t n) {
   if (g > 256 * 16) g = 256 * 16;
   return (int)g;
 }
+
+// what alpro_adamw_step_lp and alpro_adamw_step_groups ask of their buffers (`who`: the name the messages carry, `who_lp`: the mirror's)
+int adamw_check_buffers(const char* who, const char* who_lp, const float* p, const float* g, const float* m, const float* v, const float* gnorm_sq,
+                        const float* dyn_state, const void* lp, int lp_dtype) {
+  ALPRO_CHECK(!dyn_state || gnorm_sq, "%s: dynamic loss scaling needs the squared gradient norm (overflow detection)", who);
+  ALPRO_CHECK(((uintptr_t)p % 16) == 0 && ((uintptr_t)g % 16) == 0 && ((uintptr_t)m % 16) == 0 && ((uintptr_t)v % 16) == 0, "%s: buffers must be 16-byte aligned", who);
+  ALPRO_CHECK(!lp || ((lp_dtype == ALPRO_BF16 || lp_dtype == ALPRO_F16) && ((uintptr_t)lp % 8) == 0), "%s: the mirror is a 16-bit, 8-byte-aligned buffer", who_lp);
+  return ALPRO_OK;
+}
+
+// launch(typed mirror pointer): bf16_t* / f16_t* for a 16-bit mirror, (float*)nullptr for none -- the kernel's LP is the pointee
+template <typename F>
+void adamw_launch_lp(void* lp, int lp_dtype, F&& launch) {
+  if (lp && lp_dtype == ALPRO_BF16) launch((bf16_t*)lp);
+  else if (lp) launch((f16_t*)lp);
+  else launch((float*)nullptr);
+}
 }  // namespace
 }  // namespace alpro
 
@@ -307,19 +326,11 @@ extern "C" int alpro_adamw_step_lp(float* p, float* g, float* m, float* v, int64
                                    float weight_decay, float step_size, const float* gnorm_sq, float max_norm, float grad_scale,
                                    const float* dyn_state, int grads_scaled, int correct_bias, int zero_grad, void* lp, int lp_dtype, void* stream) {
   ALPRO_CHECK(p && g && m && v && n > 0, "alpro_adamw_step: bad args");
-  ALPRO_CHECK(!dyn_state || gnorm_sq, "alpro_adamw_step: dynamic loss scaling needs the squared gradient norm (overflow detection)");
-  ALPRO_CHECK(((uintptr_t)p % 16) == 0 && ((uintptr_t)g % 16) == 0 && ((uintptr_t)m % 16) == 0 && ((uintptr_t)v % 16) == 0,
-              "alpro_adamw_step: buffers must be 16-byte aligned");
-  ALPRO_CHECK(!lp || ((lp_dtype == ALPRO_BF16 || lp_dtype == ALPRO_F16) && ((uintptr_t)lp % 8) == 0), "alpro_adamw_step_lp: the mirror is a 16-bit, 8-byte-aligned buffer");
-  const dim3 grid(grid_for(n)), blk(256);
-  hipStream_t st = (hipStream_t)stream;
-#define ALPRO_ADAMW_GO(LP_, ptr)                                                                                                          \
-  hipLaunchKernelGGL(adamw_kernel<LP_>, grid, blk, 0, st, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step_size, gnorm_sq, max_norm, \
-                     grad_scale, dyn_state, grads_scaled, correct_bias, zero_grad, ptr)
-  if (lp && lp_dtype == ALPRO_BF16) ALPRO_ADAMW_GO(bf16_t, (bf16_t*)lp);
-  else if (lp) ALPRO_ADAMW_GO(f16_t, (f16_t*)lp);
-  else ALPRO_ADAMW_GO(float, (float*)nullptr);
-#undef ALPRO_ADAMW_GO
+  if (int rc = adamw_check_buffers("alpro_adamw_step", "alpro_adamw_step_lp", p, g, m, v, gnorm_sq, dyn_state, lp, lp_dtype)) return rc;
+  adamw_launch_lp(lp, lp_dtype, [&](auto* lpt) {
+    hipLaunchKernelGGL(adamw_kernel<std::remove_pointer_t<decltype(lpt)>>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1, beta2, eps,
+                       weight_decay, step_size, gnorm_sq, max_norm, grad_scale, dyn_state, grads_scaled, correct_bias, zero_grad, lpt);
+  });
   return check_launch("alpro_adamw_step");
 }
 
@@ -333,10 +344,7 @@ extern "C" int alpro_adamw_step_groups(float* p, float* g, float* m, float* v, i
   ALPRO_CHECK(segments->count <= ALPRO_ADAMW_MAX_SEGMENTS,
               "alpro_adamw_step_groups: more than ALPRO_ADAMW_MAX_SEGMENTS = " ALPRO_STR(ALPRO_ADAMW_MAX_SEGMENTS) " segments (the table travels in the kernel arguments)");
   ALPRO_CHECK(segments->count >= 1, "alpro_adamw_step_groups: an empty segment table");
-  ALPRO_CHECK(!dyn_state || gnorm_sq, "alpro_adamw_step_groups: dynamic loss scaling needs the squared gradient norm (overflow detection)");
-  ALPRO_CHECK(((uintptr_t)p % 16) == 0 && ((uintptr_t)g % 16) == 0 && ((uintptr_t)m % 16) == 0 && ((uintptr_t)v % 16) == 0,
-              "alpro_adamw_step_groups: buffers must be 16-byte aligned");
-  ALPRO_CHECK(!lp || ((lp_dtype == ALPRO_BF16 || lp_dtype == ALPRO_F16) && ((uintptr_t)lp % 8) == 0), "alpro_adamw_step_groups: the mirror is a 16-bit, 8-byte-aligned buffer");
+  if (int rc = adamw_check_buffers("alpro_adamw_step_groups", "alpro_adamw_step_groups", p, g, m, v, gnorm_sq, dyn_state, lp, lp_dtype)) return rc;
   alpro_adamw_segments_t tab = {};   // (a copy with the unused tail cleared: the kernel arguments carry no caller garbage)
   tab.count = segments->count;
   int64_t prev = 0;
@@ -348,15 +356,10 @@ extern "C" int alpro_adamw_step_groups(float* p, float* g, float* m, float* v, i
     tab.seg[k] = s;
   }
   ALPRO_CHECK(prev == n, "alpro_adamw_step_groups: the segments must cover [0, n) exactly");
-  const dim3 grid(grid_for(n)), blk(256);
-  hipStream_t st = (hipStream_t)stream;
-#define ALPRO_ADAMW_GROUPS_GO(LP_, ptr)                                                                                                  \
-  hipLaunchKernelGGL(adamw_groups_kernel<LP_>, grid, blk, 0, st, p, g, m, v, n, tab, gnorm_sq, max_norm, grad_scale, dyn_state, grads_scaled, \
-                     zero_grad, ptr)
-  if (lp && lp_dtype == ALPRO_BF16) ALPRO_ADAMW_GROUPS_GO(bf16_t, (bf16_t*)lp);
-  else if (lp) ALPRO_ADAMW_GROUPS_GO(f16_t, (f16_t*)lp);
-  else ALPRO_ADAMW_GROUPS_GO(float, (float*)nullptr);
-#undef ALPRO_ADAMW_GROUPS_GO
+  adamw_launch_lp(lp, lp_dtype, [&](auto* lpt) {
+    hipLaunchKernelGGL(adamw_groups_kernel<std::remove_pointer_t<decltype(lpt)>>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, tab, gnorm_sq,
+                       max_norm, grad_scale, dyn_state, grads_scaled, zero_grad, lpt);
+  });
   return check_launch("alpro_adamw_step_groups");
 }
 

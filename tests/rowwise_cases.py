@@ -3,7 +3,7 @@ cross-entropy and the AdamW step epilogue.  Shared by tests/test_hip_rowwise_str
 self-check); not collected itself, and nothing here touches a GPU.
 
 Every input lies on a grid that fp32 holds exactly (16-bit operands are pre-rounded to their dtype), so a kernel and its fp64 reference
-see the same operands.  The emulators restate the kernels' fp32 arithmetic in torch on the CPU (alpro_amd/csrc/core.hip ln_stats /
+see the same operands.  The emulators restate the kernels' fp32 arithmetic in torch on the CPU (alpro_amd/csrc/row768.hpp ln_stats /
 ln_affine, backward.hip row_grad, loss.hip xent_kernel, optim.hip adamw_kernel); `fault=` plants one bug at a time.  The allowance
 constants below come from the fault-free emulators against fp64 (tests/test_rowwise_cases_cpu.py re-measures them on every run), never
 from a kernel's output.
