@@ -285,31 +285,28 @@ class Block(nn.Module):
             side.ev_q = side.stream.record_event()
         return x_cls_in, cls_q, side.buf("o_c", (B * T, D), x.device)
 
-    def _cls_side_finish(self, side, ev_mid, ev_out, x_cls_in, o_c, B, T, drop_s, drop_m, x2_out, out_out):
-        """Side stream: the chain behind the attention (ev_mid: o_c -- and, training, the main path's x2 -- are written; ev_out: so is the block output)."""
+    def _cls_chain(self, x_cls_in, o_c, B, T, drop_s, drop_m, x2_out, out_out, side=None, ev_mid=None, ev_out=None):
+        """The chain behind the attention.  x_cls_in: (B, D) fp32 CLS rows of the block input (a row-strided view is fine); o_c: (B*T, D) fp32
+        attention output of the CLS query of every frame (alpro_attn_fwd's cls_out).  Writes the CLS rows before the MLP into x2_out and the CLS
+        rows of the block output into out_out (both (B, D), row-strided views of the token tensors are fine): three alpro_gemm_rows_f32 launches
+        (norm2 fused into fc1's operand load) and alpro_cls_mean_residual for the frame mean -- no torch glue in between.
+        side = None: on the launch stream, fresh buffers.  side = the block's _ClsSide: the same launches on its stream and in its buffers, behind
+        ev_mid (o_c -- and, training, the main path's x2 -- are written) and, for the last one, ev_out (so is the block output)."""
+        sa, mlp, f32, dev = self.attn, self.mlp, torch.float32, o_c.device
         D = o_c.shape[-1]
-        sa, f32, dev = self.attn, torch.float32, o_c.device
-        with torch.cuda.stream(side.stream):
-            side.stream.wait_event(ev_mid)
-            p_c = hip.gemm_rows(o_c, self._w("s_proj", sa.proj, f32), bias=sa.proj.bias, row_scale=drop_s, out=side.buf("p_c", (B * T, D), dev))
+        buf = (lambda name, rows, cols: side.buf(name, (rows, cols), dev)) if side is not None else (lambda name, rows, cols: None)
+        with torch.cuda.stream(side.stream if side is not None else None):
+            if side is not None:
+                side.stream.wait_event(ev_mid)
+            p_c = hip.gemm_rows(o_c, self._w("s_proj", sa.proj, f32), bias=sa.proj.bias, row_scale=drop_s, out=buf("p_c", B * T, D))
             hip.cls_mean_residual(x_cls_in, p_c, x2_out, B, T)
-            f1c = hip.gemm_rows(x2_out, self._w("fc1", self.mlp.fc1, f32), bias=self.mlp.fc1.bias, act=hip.ACT_GELU, ln=(self.norm2.weight, self.norm2.bias, VIT_EPS),
-                                out=side.buf("f1c", (B, self.mlp.fc1.out_features), dev))
-            side.stream.wait_event(ev_out)
-            hip.gemm_rows(f1c, self._w("fc2", self.mlp.fc2, f32), bias=self.mlp.fc2.bias, residual=x2_out, row_scale=drop_m, out=out_out)
-            side.done = side.stream.record_event()
-
-    def _cls_chain(self, x_cls_in, o_c, B, T, drop_s, drop_m, x2_out, out_out):
-        """x_cls_in: (B, D) fp32 CLS rows of the block input (a row-strided view is fine); o_c: (B*T, D) fp32 attention output of the CLS query of
-        every frame (alpro_attn_fwd's cls_out).  Writes the CLS rows before the MLP into x2_out and the CLS rows of the block output into
-        out_out (both (B, D), row-strided views of the token tensors are fine): three alpro_gemm_rows_f32 launches (norm2 fused into fc1's
-        operand load) and alpro_cls_mean_residual for the frame mean -- no torch glue in between."""
-        sa = self.attn
-        f32 = torch.float32
-        p_c = hip.gemm_rows(o_c, self._w("s_proj", sa.proj, f32), bias=sa.proj.bias, row_scale=drop_s)
-        hip.cls_mean_residual(x_cls_in, p_c, x2_out, B, T)
-        f1c = hip.gemm_rows(x2_out, self._w("fc1", self.mlp.fc1, f32), bias=self.mlp.fc1.bias, act=hip.ACT_GELU, ln=(self.norm2.weight, self.norm2.bias, VIT_EPS))
-        hip.gemm_rows(f1c, self._w("fc2", self.mlp.fc2, f32), bias=self.mlp.fc2.bias, residual=x2_out, row_scale=drop_m, out=out_out)
+            f1c = hip.gemm_rows(x2_out, self._w("fc1", mlp.fc1, f32), bias=mlp.fc1.bias, act=hip.ACT_GELU, ln=(self.norm2.weight, self.norm2.bias, VIT_EPS),
+                                out=buf("f1c", B, mlp.fc1.out_features))
+            if side is not None:
+                side.stream.wait_event(ev_out)
+            hip.gemm_rows(f1c, self._w("fc2", mlp.fc2, f32), bias=mlp.fc2.bias, residual=x2_out, row_scale=drop_m, out=out_out)
+            if side is not None:
+                side.done = side.stream.record_event()
 
     def _drop(self, rows, device):
         if not isinstance(self.drop_path, DropPath):
@@ -330,206 +327,151 @@ class Block(nn.Module):
         seed_s = rt.next_dropout_seed() if ps > 0 else 0
         return (pt if seed_t else 0.0), seed_t, (ps if seed_s else 0.0), seed_s
 
-    def _forward_halves_unfused(self, x, xf, a, B, T, N, H, D, dt, drop_t=None, drop_s=None, attn_p=0.0, attn_seed=0):
-        """The two attention halves' tails with the unmerged temporal projection (merge_temporal_proj = False): fp32 residual
-        read-modify-write in the GEMM epilogue, CLS side buffer."""
-        ta, sa = self.temporal_attn, self.attn
-        pr = hip.gemm(a, self._w("t_proj", ta.proj, dt), bias=ta.proj.bias, row_scale=drop_t, row_scale_group=T)
-        hip.gemm(pr, self._w("t_fc", self.temporal_fc, dt), out=xf, bias=self.temporal_fc.bias, out_dtype=torch.float32,
-                 residual=xf, map_mode=hip.MAP_SKIP_CLS, map_p0=N * T)
-        hs = hip.layernorm(x, self.norm1.weight, self.norm1.bias, VIT_EPS, dt, rows=B * T * (N + 1),
-                           map_mode=hip.MAP_FRAME_TOKENS, map_p0=T, map_p1=N)
-        qkv = hip.gemm(hs, self._w("s_qkv", sa.qkv, dt), bias=sa.qkv.bias)
-        a = hip.attn(qkv, B * T, N + 1, H, sa.scale, drop_p=attn_p, drop_seed=attn_seed)
-        side = torch.empty((B * T, D), dtype=torch.float32, device=x.device)
-        hip.gemm(a, self._w("s_proj", sa.proj, dt), out=xf, bias=sa.proj.bias, out_dtype=torch.float32, residual=xf,
-                 row_scale=drop_s, row_scale_group=N + 1,
-                 map_mode=hip.MAP_FRAME_TOKENS, map_p0=T, map_p1=N, side=side)
-        hip.cls_mean_residual(x, side, x, B, T)
-
     def forward(self, x, B, T, W):
         """x: (B, 1 + N*T, D) fp32 contiguous token tensor; updated IN PLACE and returned (inference path)."""
-        dt = rt.compute_dtype()
-        S, D = x.shape[1], x.shape[2]
-        N = (S - 1) // T
-        H = self.attn.num_heads
-        xf = x.view(B * S, D)
-        ta, sa = self.temporal_attn, self.attn
-        drop_t, drop_s, drop_m = self._drop(B * N, x.device), self._drop(B * T, x.device), self._drop(B, x.device)
-        ap_t, seed_t, ap_s, seed_s = self._attn_drop_seeds()
-        cp = rt.cls_precise(dt) and self.merge_temporal_proj
-        side = _ClsSide.get(x.device) if (cp and rt.cls_stream(False) and x.is_cuda) else None
-        if side is not None:
-            x_cls_in, cls_q, o_c_buf = self._cls_side_begin(side, x, B, T, snapshot=True)
-        else:
-            x_cls_in = x[:, 0].clone() if cp else None   # a COPY (x is updated in place below; .contiguous() of a one-clip batch is a view); the temporal half never touches the CLS row
-        # ---- temporal (vit.py:146-162)
-        h = hip.layernorm(x, self.temporal_norm1.weight, self.temporal_norm1.bias, VIT_EPS, dt, rows=B * N * T,
-                          map_mode=hip.MAP_SKIP_CLS, map_p0=N * T)
-        if rt.fuse_temporal_attention() and hip.qkv_tattn_ok(h, T) and ta.qkv.bias is not None and not seed_t:   # (the fused launch has no dropout)
-            # round 6: qkv Linear + frame attention in one launch, q | k | v consumed out of the accumulators (alpro_gemm_qkv_tattn) -- the
-            # (B*N*T, 2304) tensor is never written.  Forward only: forward_train keeps the two launches, whose backward needs q, k, v
-            a = hip.gemm_qkv_tattn(h, self._w("t_qkv", ta.qkv, dt), ta.qkv.bias, T, H, ta.scale)
-        else:
-            qkv = hip.gemm(h, self._w("t_qkv", ta.qkv, dt), bias=ta.qkv.bias)
-            a = hip.attn_temporal(qkv, T, H, ta.scale, drop_p=ap_t, drop_seed=seed_t)
-        if self.merge_temporal_proj:
-            # round 3: the two N = 768 projections write 16-bit deltas in plain row order; residual add + row maps + LayerNorm are one
-            # streaming kernel each (alpro_add_layernorm_fwd) -- see the kernel's header comment in csrc/core.hip
-            mg = self._merged_tproj(dt)
-            d_t = hip.gemm(a, mg["w"], bias=mg["b1"], row_scale=drop_t, row_scale_group=T)
-            if side is not None:
-                side.wait_done()   # the previous block's chain has written this block's input CLS rows (first read: the kernel below)
-            # round 6 (alpro_amd.config.defer_temporal_add): x + temporal branch (vit.py:162) is not written here -- the add + norm2 kernel below
-            # adds both branches to the block input in the same order of fp32 additions (bit for bit the same x')
-            defer = rt.defer_temporal_add()
-            hs, _ = hip.add_layernorm(x, d_t, self.norm1.weight, self.norm1.bias, VIT_EPS, mode=hip.ADD_PRE_SPATIAL, x_out=None if defer else x,
-                                      want_x=not defer, delta_bias=self.temporal_fc.bias, T=T, N=N)
-            qkv = hip.gemm(hs, self._w("s_qkv", sa.qkv, dt), bias=sa.qkv.bias)
-            if side is not None:
-                torch.cuda.current_stream().wait_event(side.ev_q)
-                a, o_c = hip.attn(qkv, B * T, N + 1, H, sa.scale, cls_q=cls_q, cls_group=T, cls_out=o_c_buf, drop_p=ap_s, drop_seed=seed_s)
-                ev_attn = torch.cuda.current_stream().record_event()
-            elif cp:   # the CLS query of every frame once more in fp32, inside the same attention launch
-                a, o_c = hip.attn(qkv, B * T, N + 1, H, sa.scale, cls_q=self._cls_qkv(x_cls_in), cls_group=T, drop_p=ap_s, drop_seed=seed_s)
-            else:
-                a = hip.attn(qkv, B * T, N + 1, H, sa.scale, drop_p=ap_s, drop_seed=seed_s)
-            d_s = hip.gemm(a, self._w("s_proj", sa.proj, dt), bias=sa.proj.bias, row_scale=drop_s, row_scale_group=N + 1)
-            if defer:
-                h2 = hip.add_layernorm_pre_mlp2(x, d_t, self.temporal_fc.bias, d_s, self.norm2.weight, self.norm2.bias, VIT_EPS, T, N, x_out=x)
-            else:
-                h2, _ = hip.add_layernorm(x, d_s, self.norm2.weight, self.norm2.bias, VIT_EPS, mode=hip.ADD_PRE_MLP, x_out=x, T=T, N=N)
-        else:
-            self._forward_halves_unfused(x, xf, a, B, T, N, H, D, dt, drop_t, drop_s, attn_p=ap_s, attn_seed=seed_s)
-            h2 = hip.layernorm(x, self.norm2.weight, self.norm2.bias, VIT_EPS, dt)
-        f1 = hip.gemm(h2, self._w("fc1", self.mlp.fc1, dt), bias=self.mlp.fc1.bias, act=hip.ACT_GELU)
-        hip.gemm(f1, self._w("fc2", self.mlp.fc2, dt), out=xf, bias=self.mlp.fc2.bias, out_dtype=torch.float32, residual=xf,
-                 row_scale=drop_m, row_scale_group=S)
-        if side is not None:
-            self._cls_side_finish(side, ev_attn, torch.cuda.current_stream().record_event(), x_cls_in, o_c, B, T, drop_s, drop_m,
-                                  side.buf("x2_c", (B, D), x.device), x[:, 0])
-        elif cp:
-            self._cls_chain(x_cls_in, o_c, B, T, drop_s, drop_m, torch.empty_like(x_cls_in), x[:, 0])
-        return x
+        return self._forward(x, B, T)
 
-    # ---- training path: fresh buffers (the backward needs every LayerNorm input), explicit backward ----------
     def forward_train(self, x, B, T, W):
-        """Same arithmetic as forward() but out of place; returns (out, saved)."""
-        dt = rt.compute_dtype()
-        S, D = x.shape[1], x.shape[2]
-        N = (S - 1) // T
-        H = self.attn.num_heads
-        ta, sa = self.temporal_attn, self.attn
-        dev = x.device
-        sv = {"x": x, "dims": (B, T, N, S, D, H), "dt": dt}
-        sv["drop_t"], sv["drop_s"], sv["drop_m"] = self._drop(B * N, dev), self._drop(B * T, dev), self._drop(B, dev)
-        ap_t, seed_t, ap_s, seed_s = sv["attn_drop"] = self._attn_drop_seeds()   # the backward regenerates the masks from these
-        cside = None
-        if rt.cls_precise(dt) and rt.cls_stream(True) and x.is_cuda and self.merge_temporal_proj:
-            cside = _ClsSide.get(dev)
-            x_cls_in, cls_q, o_c_buf = self._cls_side_begin(cside, x, B, T, snapshot=False)
-        h = hip.layernorm(x, self.temporal_norm1.weight, self.temporal_norm1.bias, VIT_EPS, dt, rows=B * N * T,
-                          map_mode=hip.MAP_SKIP_CLS, map_p0=N * T)
-        if rt.fuse_temporal_attention(training=True) and hip.qkv_tattn_ok(h, T) and ta.qkv.bias is not None and not seed_t:   # (the fused launch has no dropout)
-            # round 6 (ALPRO_FUSE_TATTN=1; off by default: alpro_amd/config.py): one launch; q | k | v are still written (the backward reads them), what goes away is the attention launch and its re-read
-            a_t, qkv_t, lse_t = hip.gemm_qkv_tattn(h, self._w("t_qkv", ta.qkv, dt), ta.qkv.bias, T, H, ta.scale, want_qkv=True)
-        else:
-            qkv_t = hip.gemm(h, self._w("t_qkv", ta.qkv, dt), bias=ta.qkv.bias)
-            a_t, lse_t = hip.attn_temporal(qkv_t, T, H, ta.scale, want_lse=True, drop_p=ap_t, drop_seed=seed_t)
-        sv["merged"] = self.merge_temporal_proj
-        if self.merge_temporal_proj:
-            pr = None
-            mg = self._merged_tproj(dt)
-            d_t = hip.gemm(a_t, mg["w"], bias=mg["b1"], row_scale=sv["drop_t"], row_scale_group=T)
-            if cside is not None:
-                cside.wait_done()   # the previous block's chain has written this block's input CLS rows (first read: the kernel below)
-            hs, xt = hip.add_layernorm(x, d_t, self.norm1.weight, self.norm1.bias, VIT_EPS, mode=hip.ADD_PRE_SPATIAL,
-                                       delta_bias=self.temporal_fc.bias, T=T, N=N)
-            del d_t
-            qkv_s = hip.gemm(hs, self._w("s_qkv", sa.qkv, dt), bias=sa.qkv.bias)
-            o_c = None
-            if cside is not None:
-                torch.cuda.current_stream().wait_event(cside.ev_q)
-                a_s, lse_s, o_c = hip.attn(qkv_s, B * T, N + 1, H, sa.scale, want_lse=True, cls_q=cls_q, cls_group=T, cls_out=o_c_buf, drop_p=ap_s, drop_seed=seed_s)
-            elif rt.cls_precise(dt):
-                a_s, lse_s, o_c = hip.attn(qkv_s, B * T, N + 1, H, sa.scale, want_lse=True, cls_q=self._cls_qkv(x[:, 0]), cls_group=T, drop_p=ap_s, drop_seed=seed_s)
-            else:
-                a_s, lse_s = hip.attn(qkv_s, B * T, N + 1, H, sa.scale, want_lse=True, drop_p=ap_s, drop_seed=seed_s)
-            d_s = hip.gemm(a_s, self._w("s_proj", sa.proj, dt), bias=sa.proj.bias, row_scale=sv["drop_s"], row_scale_group=N + 1)
-            h2, x2 = hip.add_layernorm(xt, d_s, self.norm2.weight, self.norm2.bias, VIT_EPS, mode=hip.ADD_PRE_MLP, T=T, N=N)
-            del d_s
-            if cside is not None:
-                ev_x2 = torch.cuda.current_stream().record_event()   # o_c and the main path's x2 (whose CLS rows the chain overwrites) are written
-        else:
-            xt = torch.empty_like(x)
-            xt[:, 0] = x[:, 0]
-            pr = hip.gemm(a_t, self._w("t_proj", ta.proj, dt), bias=ta.proj.bias, row_scale=sv["drop_t"], row_scale_group=T)
-            hip.gemm(pr, self._w("t_fc", self.temporal_fc, dt), out=xt.view(B * S, D), bias=self.temporal_fc.bias, out_dtype=torch.float32,
-                     residual=x.view(B * S, D), map_mode=hip.MAP_SKIP_CLS, map_p0=N * T)
-            hs = hip.layernorm(xt, self.norm1.weight, self.norm1.bias, VIT_EPS, dt, rows=B * T * (N + 1),
-                               map_mode=hip.MAP_FRAME_TOKENS, map_p0=T, map_p1=N)
-            qkv_s = hip.gemm(hs, self._w("s_qkv", sa.qkv, dt), bias=sa.qkv.bias)
-            a_s, lse_s = hip.attn(qkv_s, B * T, N + 1, H, sa.scale, want_lse=True, drop_p=ap_s, drop_seed=seed_s)
-            x2 = torch.empty_like(x)
-            side = torch.empty((B * T, D), dtype=torch.float32, device=dev)
-            hip.gemm(a_s, self._w("s_proj", sa.proj, dt), out=x2.view(B * S, D), bias=sa.proj.bias, out_dtype=torch.float32,
-                     residual=xt.view(B * S, D), row_scale=sv["drop_s"], row_scale_group=N + 1,
-                     map_mode=hip.MAP_FRAME_TOKENS, map_p0=T, map_p1=N, side=side)
-            hip.cls_mean_residual(xt, side, x2, B, T)
-            h2 = hip.layernorm(x2, self.norm2.weight, self.norm2.bias, VIT_EPS, dt)
-        u, sv["u_tiled"] = tr.gelu_save_buffer(B * S, self.mlp.fc1.out_features, D, dt, dev)
-        # u holds gelu'(fc1 output) (round 3) rather than the fc1 output itself (round 5: in the GEMM's tile order)
-        f1 = hip.gemm(h2, self._w("fc1", self.mlp.fc1, dt), bias=self.mlp.fc1.bias, act=hip.ACT_GELU_SAVE_GRAD, pre_act=u,
-                      c2_tiled=sv["u_tiled"])
-        out = torch.empty_like(x)
-        hip.gemm(f1, self._w("fc2", self.mlp.fc2, dt), out=out.view(B * S, D), bias=self.mlp.fc2.bias, out_dtype=torch.float32,
-                 residual=x2.view(B * S, D), row_scale=sv["drop_m"], row_scale_group=S)
-        if cside is not None:
-            self._cls_side_finish(cside, ev_x2, torch.cuda.current_stream().record_event(), x_cls_in, o_c, B, T, sv["drop_s"], sv["drop_m"], x2[:, 0], out[:, 0])
-        elif rt.cls_precise(dt) and self.merge_temporal_proj:
-            # precise CLS rows: the block output's CLS row and the saved pre-MLP stream's CLS row (norm2's backward input) take the fp32 values;
-            # the backward differentiates the 16-bit graph as before (its CLS-row operands differ from these by one rounding)
-            self._cls_chain(x[:, 0], o_c, B, T, sv["drop_s"], sv["drop_m"], x2[:, 0], out[:, 0])
-        sv.update(h=h, qkv_t=qkv_t, a_t=a_t, lse_t=lse_t, pr=pr, xt=xt, hs=hs, qkv_s=qkv_s, a_s=a_s, lse_s=lse_s, x2=x2, h2=h2, u=u, f1=f1)
-        return out, sv
+        """Same arithmetic as forward() but out of place: fresh buffers (the backward needs every LayerNorm input); returns (out, saved) for the
+        explicit backward()."""
+        return self._forward(x, B, T, save=True)
 
     def forward_cls(self, x, B, T, W):
         """LAST block when only the CLS output is consumed (the frozen prompter: get_pseudo_labels uses feat = proj(x[:, 0])):
         the temporal half and the spatial K/V need every token, but the spatial projection, the MLP and what follows are
         evaluated on the CLS rows alone -- (B*T, D) / (B, D) instead of (B*S, D).  Same arithmetic as forward() for those rows
         (vit.py:165-212); eval mode only (no drop-path).  Returns the block output's CLS rows, (B, D) fp32."""
+        return self._forward(x, B, T, cls_only=True)
+
+    def _forward(self, x, B, T, save=False, cls_only=False):
+        """The divided space-time block (vit.py:146-212), every stage stated once.  The residual stream goes
+            x --temporal branch--> xt --spatial branch--> x2 --MLP--> out
+        and the three entry points differ in where those four live and in what is kept:
+            forward        all four ARE x; with the merged projection xt is never written (its add rides in the add + norm2 kernel)
+            forward_train  save: a fresh tensor each, q | k | v, the log-sum-exp rows and gelu' kept -> (out, saved)
+            forward_cls    cls_only: as forward up to the spatial attention, the rest on the CLS rows -> their (B, D) output rows"""
         dt = rt.compute_dtype()
         S, D = x.shape[1], x.shape[2]
         N = (S - 1) // T
         H = self.attn.num_heads
+        ta, sa, fc, mlp, dev, f32 = self.temporal_attn, self.attn, self.temporal_fc, self.mlp, x.device, torch.float32
+        merged = self.merge_temporal_proj
         xf = x.view(B * S, D)
-        ta, sa = self.temporal_attn, self.attn
+        if cls_only:   # eval mode only: no drop-path mask and no dropout seed is drawn (the seed stream of later BERT layers does not shift)
+            drop_t = drop_s = drop_m = None
+            rs_t = rs_s = rs_m = {}
+            seeds = ap_t, seed_t, ap_s, seed_s = 0.0, 0, 0.0, 0
+        else:
+            drop_t, drop_s, drop_m = self._drop(B * N, dev), self._drop(B * T, dev), self._drop(B, dev)
+            rs_t, rs_s, rs_m = (dict(row_scale=d, row_scale_group=g) for d, g in ((drop_t, T), (drop_s, N + 1), (drop_m, S)))
+            seeds = ap_t, seed_t, ap_s, seed_s = self._attn_drop_seeds()   # the backward regenerates the masks from these
+        # precise CLS rows, decided once: off (cp False) | on the launch stream (cp, side None) | on the side stream (side)
+        cp = merged and not cls_only and rt.cls_precise(dt)
+        side = _ClsSide.get(dev) if (cp and rt.cls_stream(save) and x.is_cuda) else None
+        ev_mid = None
+        if side is not None:
+            x_cls_in, cls_q, o_c_buf = self._cls_side_begin(side, x, B, T, snapshot=not save)
+        elif cp:   # in place: a COPY (x is updated below; .contiguous() of a one-clip batch is a view); the temporal half never touches the CLS row
+            x_cls_in = x[:, 0] if save else x[:, 0].clone()
+        # ---- temporal attention (vit.py:146-156)
         h = hip.layernorm(x, self.temporal_norm1.weight, self.temporal_norm1.bias, VIT_EPS, dt, rows=B * N * T,
                           map_mode=hip.MAP_SKIP_CLS, map_p0=N * T)
-        if rt.fuse_temporal_attention() and hip.qkv_tattn_ok(h, T) and ta.qkv.bias is not None:
-            a = hip.gemm_qkv_tattn(h, self._w("t_qkv", ta.qkv, dt), ta.qkv.bias, T, H, ta.scale)
+        w_qkv = self._w("t_qkv", ta.qkv, dt)
+        if rt.fuse_temporal_attention(training=save) and hip.qkv_tattn_ok(h, T) and ta.qkv.bias is not None and not seed_t:   # (the fused launch has no dropout)
+            # round 6: qkv Linear + frame attention in one launch, q | k | v consumed out of the accumulators (alpro_gemm_qkv_tattn).  No-grad: the
+            # (B*N*T, 2304) tensor is never written.  Training (ALPRO_FUSE_TATTN=1; off by default: alpro_amd/config.py): q | k | v are still
+            # written (the backward reads them), what goes away is the attention launch and its re-read
+            r = hip.gemm_qkv_tattn(h, w_qkv, ta.qkv.bias, T, H, ta.scale, want_qkv=save)
+            a_t, qkv_t, lse_t = r if save else (r, None, None)
         else:
-            qkv = hip.gemm(h, self._w("t_qkv", ta.qkv, dt), bias=ta.qkv.bias)
-            a = hip.attn_temporal(qkv, T, H, ta.scale)
-        if self.merge_temporal_proj:
+            qkv_t = hip.gemm(h, w_qkv, bias=ta.qkv.bias)
+            r = hip.attn_temporal(qkv_t, T, H, ta.scale, want_lse=save, drop_p=ap_t, drop_seed=seed_t)
+            a_t, lse_t = r if save else (r, None)
+        del r
+        # ---- temporal projection, x -> xt, norm1 in frame-token order (vit.py:157-172, 180)
+        pr = None
+        if merged:
+            # round 3: the two N = 768 projections write 16-bit deltas in plain row order; residual add + row maps + LayerNorm are one
+            # streaming kernel each (alpro_add_layernorm_fwd) -- see the kernel's header comment in csrc/core.hip
             mg = self._merged_tproj(dt)
-            d_t = hip.gemm(a, mg["w"], bias=mg["b1"])
-            hs, _ = hip.add_layernorm(x, d_t, self.norm1.weight, self.norm1.bias, VIT_EPS, mode=hip.ADD_PRE_SPATIAL, want_x=False,
-                                      delta_bias=self.temporal_fc.bias, T=T, N=N)   # the patch rows of x are not read again; x[:, 0] is untouched
-        else:
-            pr = hip.gemm(a, self._w("t_proj", ta.proj, dt), bias=ta.proj.bias)
-            hip.gemm(pr, self._w("t_fc", self.temporal_fc, dt), out=xf, bias=self.temporal_fc.bias, out_dtype=torch.float32,
-                     residual=xf, map_mode=hip.MAP_SKIP_CLS, map_p0=N * T)
-            hs = hip.layernorm(x, self.norm1.weight, self.norm1.bias, VIT_EPS, dt, rows=B * T * (N + 1),
+            d_t = hip.gemm(a_t, mg["w"], bias=mg["b1"], **rs_t)
+            if side is not None:
+                side.wait_done()   # the previous block's chain has written this block's input CLS rows (first read: the kernel below)
+            # round 6 (alpro_amd.config.defer_temporal_add): in place, x + temporal branch (vit.py:162) is not written here -- the add + norm2 kernel
+            # below adds both branches to the block input in the same order of fp32 additions (bit for bit the same x').  forward_cls never needs
+            # it: the patch rows of x are not read again and x[:, 0] is untouched
+            defer = not save and (cls_only or rt.defer_temporal_add())
+            hs, xt = hip.add_layernorm(x, d_t, self.norm1.weight, self.norm1.bias, VIT_EPS, mode=hip.ADD_PRE_SPATIAL,
+                                       x_out=None if (save or defer) else x, want_x=not defer, delta_bias=fc.bias, T=T, N=N)
+            if defer:
+                xt = x
+            else:
+                del d_t
+        else:   # the two Linears as written, fp32 residual read-modify-write in the GEMM epilogue (the tests' oracle for the merged form)
+            xt = x
+            if save:
+                xt = torch.empty_like(x)
+                xt[:, 0] = x[:, 0]
+            pr = hip.gemm(a_t, self._w("t_proj", ta.proj, dt), bias=ta.proj.bias, **rs_t)
+            hip.gemm(pr, self._w("t_fc", fc, dt), out=xt.view(B * S, D), bias=fc.bias, out_dtype=f32, residual=xf,
+                     map_mode=hip.MAP_SKIP_CLS, map_p0=N * T)
+            hs = hip.layernorm(xt, self.norm1.weight, self.norm1.bias, VIT_EPS, dt, rows=B * T * (N + 1),
                                map_mode=hip.MAP_FRAME_TOKENS, map_p0=T, map_p1=N)
-        qkv = hip.gemm(hs, self._w("s_qkv", sa.qkv, dt), bias=sa.qkv.bias)
-        a = hip.attn(qkv, B * T, N + 1, H, sa.scale)
-        a_cls = a.view(B * T, N + 1, D)[:, 0].contiguous()                                  # CLS query of every frame
-        p_cls = hip.gemm(a_cls, self._w("s_proj", sa.proj, dt), bias=sa.proj.bias, out_dtype=torch.float32)
-        x_cls = x[:, 0] + p_cls.view(B, T, D).mean(1)                                        # frame mean of the CLS rows (vit.py:187)
-        h2 = hip.layernorm(x_cls.contiguous(), self.norm2.weight, self.norm2.bias, VIT_EPS, dt)
-        f1 = hip.gemm(h2, self._w("fc1", self.mlp.fc1, dt), bias=self.mlp.fc1.bias, act=hip.ACT_GELU)
-        return hip.gemm(f1, self._w("fc2", self.mlp.fc2, dt), bias=self.mlp.fc2.bias, out_dtype=torch.float32, residual=x_cls.contiguous())
+        # ---- spatial attention (vit.py:180), the CLS query of every frame once more in fp32 inside the same launch if cp
+        qkv_s = hip.gemm(hs, self._w("s_qkv", sa.qkv, dt), bias=sa.qkv.bias)
+        cq = {}
+        if side is not None:
+            torch.cuda.current_stream().wait_event(side.ev_q)
+            cq = dict(cls_q=cls_q, cls_group=T, cls_out=o_c_buf)
+        elif cp:
+            cq = dict(cls_q=self._cls_qkv(x_cls_in), cls_group=T)
+        r = hip.attn(qkv_s, B * T, N + 1, H, sa.scale, want_lse=save, drop_p=ap_s, drop_seed=seed_s, **cq)
+        r = r if isinstance(r, tuple) else (r,)   # out [, lse] [, cls_out]
+        a_s, lse_s, o_c = r[0], (r[1] if save else None), (r[-1] if cp else None)
+        del r, cq
+        if side is not None and not save:
+            ev_mid = torch.cuda.current_stream().record_event()   # o_c is written
+        # ---- spatial projection, xt -> x2, norm2 (vit.py:184-200)
+        if cls_only:   # CLS query of every frame -> projection -> frame mean of the CLS rows (vit.py:187)
+            a_cls = a_s.view(B * T, N + 1, D)[:, 0].contiguous()
+            p_cls = hip.gemm(a_cls, self._w("s_proj", sa.proj, dt), bias=sa.proj.bias, out_dtype=f32)
+            x2 = (x[:, 0] + p_cls.view(B, T, D).mean(1)).contiguous()
+            h2 = hip.layernorm(x2, self.norm2.weight, self.norm2.bias, VIT_EPS, dt)
+        elif merged:
+            d_s = hip.gemm(a_s, self._w("s_proj", sa.proj, dt), bias=sa.proj.bias, **rs_s)
+            if defer:
+                h2, x2 = hip.add_layernorm_pre_mlp2(x, d_t, fc.bias, d_s, self.norm2.weight, self.norm2.bias, VIT_EPS, T, N, x_out=x), x
+            else:
+                h2, x2 = hip.add_layernorm(xt, d_s, self.norm2.weight, self.norm2.bias, VIT_EPS, mode=hip.ADD_PRE_MLP, x_out=None if save else x, T=T, N=N)
+            del d_s
+            if side is not None and save:
+                ev_mid = torch.cuda.current_stream().record_event()   # o_c and the main path's x2 (whose CLS rows the chain overwrites) are written
+        else:   # CLS side buffer: the epilogue leaves the frames' CLS deltas there, alpro_cls_mean_residual adds their mean
+            x2 = torch.empty_like(x) if save else x
+            cls_rows = torch.empty((B * T, D), dtype=f32, device=dev)
+            hip.gemm(a_s, self._w("s_proj", sa.proj, dt), out=x2.view(B * S, D), bias=sa.proj.bias, out_dtype=f32, residual=xt.view(B * S, D), **rs_s,
+                     map_mode=hip.MAP_FRAME_TOKENS, map_p0=T, map_p1=N, side=cls_rows)
+            hip.cls_mean_residual(xt, cls_rows, x2, B, T)
+            h2 = hip.layernorm(x2, self.norm2.weight, self.norm2.bias, VIT_EPS, dt)
+        # ---- MLP, x2 -> out (vit.py:198-212)
+        u, u_tiled = tr.gelu_save_buffer(B * S, mlp.fc1.out_features, D, dt, dev) if save else (None, False)
+        # u holds gelu'(fc1 output) (round 3) rather than the fc1 output itself (round 5: in the GEMM's tile order)
+        f1 = hip.gemm(h2, self._w("fc1", mlp.fc1, dt), bias=mlp.fc1.bias, act=hip.ACT_GELU_SAVE_GRAD if save else hip.ACT_GELU, pre_act=u, c2_tiled=u_tiled)
+        out = hip.gemm(f1, self._w("fc2", mlp.fc2, dt), out=None if (save or cls_only) else xf, bias=mlp.fc2.bias, out_dtype=f32,
+                       residual=x2.view(-1, D), **rs_m)
+        if cls_only:
+            return out
+        out = out.view(B, S, D) if save else x
+        if cp:
+            # precise CLS rows: the block output's CLS row and (training) the saved pre-MLP stream's CLS row (norm2's backward input) take the fp32
+            # values; the backward differentiates the 16-bit graph as before (its CLS-row operands differ from these by one rounding)
+            ev_out = torch.cuda.current_stream().record_event() if side is not None else None
+            x2_c = x2[:, 0] if save else (side.buf("x2_c", (B, D), dev) if side is not None else torch.empty_like(x_cls_in))
+            self._cls_chain(x_cls_in, o_c, B, T, drop_s, drop_m, x2_c, out[:, 0], side, ev_mid, ev_out)
+        if not save:
+            return out
+        return out, dict(x=x, dims=(B, T, N, S, D, H), dt=dt, drop_t=drop_t, drop_s=drop_s, drop_m=drop_m, attn_drop=seeds, merged=merged, u_tiled=u_tiled,
+                         h=h, qkv_t=qkv_t, a_t=a_t, lse_t=lse_t, pr=pr, xt=xt, hs=hs, qkv_s=qkv_s, a_s=a_s, lse_s=lse_s, x2=x2, h2=h2, u=u, f1=f1)
 
     def _wt(self, name, lin, dt):
         return tr.transposed_operand(self._ops, name + "^T", lin.weight, dt)
