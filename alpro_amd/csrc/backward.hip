@@ -1,5 +1,5 @@
 // Memory-bound backward kernels: transposes feeding the NT GEMM for dgrad / wgrad, LayerNorm backward
-// (with the row maps of the forward gather turned into scatters), CLS-mean / final-pool / BERT-embedding
+// (with the row maps of the forward gather turned into scatters), CLS-mean / final-pool (all three pooling modes) / BERT-embedding
 // backward, and the GELU-gradient multiply.  All HBM-bound; 16-byte accesses wherever rows are contiguous.
 #include "common.hpp"
 #include "row768.hpp"
@@ -296,6 +296,88 @@ __global__ __launch_bounds__(192) void cls_rows_reduce_kernel(const float* __res
   float4* o = (float4*)(dx + (int64_t)b * (1 + (int64_t)N * T) * ld_dx + c);
   const float4 cur = *o;
   *o = make_float4(cur.x + s.x, cur.y + s.y, cur.z + s.z, cur.w + s.w);
+}
+
+// ---- final norm + pooling backward (ALPRO_POOL_*): the un-pooling folded into the LayerNorm backward -------------------------------------
+// One wave per TOKEN row r = b*S + k of x, so dx has one writer per row and needs neither a map nor accumulation; the row's dy is read out of
+// the pooled gradient where it lies (patch n, frame t):
+//   TEMPORAL  dout (B, 1+N):    k = 0: dout[b, 0];  else dout[b, 1+n] / T
+//   SPATIAL   dout (B, 1+T):    k = 0: dout[b, 0];  else dout[b, 1+t] / N
+//   NONE      dout (B, T, 1+N): k = 0: sum_t dout[b, t, 0] (t ascending);  else dout[b, t, 1+n]
+// The arithmetic of a row, the dgamma / dbeta partials (part[workgroup][2][768] for colsum_reduce_kernel, or atomics) and the ROWS emit are
+// those of layernorm_bwd_kernel; that kernel's own code stays as it is (it is shared with every other LayerNorm of the path).
+template <typename TE, int MODE>
+__global__ __launch_bounds__(256) void vit_final_pool_bwd_kernel(const float* __restrict__ dout, const float* __restrict__ x, const float* __restrict__ gamma,
+                                                                 float eps, float* __restrict__ dx, float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                                                 int64_t rows, int Tn, int N, const EmitArgs em, float* __restrict__ part) {
+  __shared__ float red[2][4][LN_D];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int64_t nwaves = (int64_t)gridDim.x * 4;
+  const int64_t S = 1 + (int64_t)N * Tn;
+  float g[12], ag[12], ab[12], cp[12];
+  ln_load(gamma, lane, g);
+#pragma unroll
+  for (int i = 0; i < 12; ++i) ag[i] = ab[i] = cp[i] = 0.f;
+  for (int64_t r = (int64_t)blockIdx.x * 4 + w; r < rows; r += nwaves) {
+    const int64_t b = r / S, k = r - b * S;
+    const int64_t n = k ? (k - 1) / Tn : 0;
+    const int t = k ? (int)((k - 1) - n * Tn) : 0;
+    int64_t src;     // row of dout
+    float sc = 1.0f;
+    if constexpr (MODE == ALPRO_POOL_TEMPORAL) {
+      src = b * (N + 1) + (k ? 1 + n : 0);
+      if (k) sc = 1.0f / (float)Tn;
+    } else if constexpr (MODE == ALPRO_POOL_SPATIAL) {
+      src = b * (Tn + 1) + (k ? 1 + t : 0);
+      if (k) sc = 1.0f / (float)N;
+    } else {
+      src = (b * Tn + t) * (N + 1) + (k ? 1 + n : 0);
+    }
+    float xv[12], d[12];
+    ln_load_nt(x + r * LN_D, lane, xv);
+    ln_load(dout + src * LN_D, lane, d);   // plain: a pooled row is read by the T (N) token rows it was averaged over
+    if (MODE == ALPRO_POOL_NONE && k == 0) {
+      for (int f = 1; f < Tn; ++f) {
+        float d2[12];
+        ln_load(dout + (src + (int64_t)f * (N + 1)) * LN_D, lane, d2);
+#pragma unroll
+        for (int i = 0; i < 12; ++i) d[i] += d2[i];
+      }
+    }
+    float mean, rstd;
+    ln_stats(xv, eps, mean, rstd);
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int i = 0; i < 12; ++i) {
+      d[i] *= sc;
+      xv[i] = (xv[i] - mean) * rstd;  // xhat
+      ab[i] += d[i];
+      ag[i] += d[i] * xv[i];
+      d[i] *= g[i];
+      s1 += d[i];
+      s2 += d[i] * xv[i];
+    }
+    s1 = wave_sum(s1) * (1.0f / LN_D);
+    s2 = wave_sum(s2) * (1.0f / LN_D);
+    float fin[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) fin[i] = rstd * (d[i] - s1 - xv[i] * s2);
+    ln_store<float>(dx + r * LN_D, lane, fin);
+    if (em.mode != ALPRO_EMIT_NONE) emit_row<TE>(em, r, lane, fin, cp);
+  }
+#pragma unroll
+  for (int i = 0; i < 12; ++i) {
+    red[0][w][row_col(lane, i)] = ag[i];
+    red[1][w][row_col(lane, i)] = ab[i];
+  }
+  __syncthreads();
+  float* slot = part ? part + (int64_t)blockIdx.x * (2 * LN_D) : nullptr;
+  for (int c = threadIdx.x; c < LN_D; c += 256) {
+    const float sg = red[0][0][c] + red[0][1][c] + red[0][2][c] + red[0][3][c];
+    const float sb = red[1][0][c] + red[1][1][c] + red[1][2][c] + red[1][3][c];
+    if (slot) { slot[c] = sg; slot[LN_D + c] = sb; }
+    else { atomicAdd(dgamma + c, sg); atomicAdd(dbeta + c, sb); }
+  }
 }
 
 // ---- out[m, :] = (T)(scale(m) * src[row(m), :]): gathers fp32 token-gradient rows into a GEMM operand ---------------
@@ -656,6 +738,38 @@ extern "C" int alpro_layernorm_bwd(const void* dy, int dy_dtype, int64_t ld_dy, 
                                    size_t workspace_bytes, void* stream) {
   return alpro_layernorm_bwd_emit(dy, dy_dtype, ld_dy, dy2, x, ldx, gamma, eps, dx, ld_dx, accumulate, dgamma, dbeta, rows, D, map_mode, map_p0, map_p1,
                                   drop_p, drop_seed, nullptr, dy_dtype, ALPRO_EMIT_NONE, 0, 0, nullptr, 1, 0.f, 0u, nullptr, 0, workspace, workspace_bytes, stream);
+}
+
+extern "C" int alpro_vit_final_pool_mode_bwd(const float* dout, const float* x, const float* gamma, float eps, float* dx, float* dgamma, float* dbeta,
+                                             int mode, int64_t rows, int B, int T, int N, int D, void* emit_out, int emit_dtype, const float* emit_scale,
+                                             int emit_scale_group, void* workspace, size_t workspace_bytes, void* stream) {
+  constexpr size_t part_bytes = 2 * LN_D * sizeof(float);  // one workgroup's column sums: dgamma | dbeta
+  ALPRO_CHECK(dout && x && gamma && dx && dgamma && dbeta && B > 0 && T > 0 && N > 0, "alpro_vit_final_pool_mode_bwd: bad args");
+  ALPRO_CHECK(mode >= ALPRO_POOL_TEMPORAL && mode <= ALPRO_POOL_NONE, "alpro_vit_final_pool_mode_bwd: bad mode %d (ALPRO_POOL_TEMPORAL / _SPATIAL / _NONE)", mode);
+  ALPRO_CHECK(D == LN_D, "alpro_vit_final_pool_mode_bwd: D=%d unsupported (hidden size is 768 on this path)", D);
+  ALPRO_CHECK(rows == (int64_t)B * (1 + (int64_t)N * T), "alpro_vit_final_pool_mode_bwd: rows=%lld is not B * (1 + N * T) = %d * (1 + %d * %d)", (long long)rows, B, N, T);
+  ALPRO_CHECK(!workspace || (((uintptr_t)workspace % 16) == 0 && workspace_bytes >= part_bytes), "alpro_vit_final_pool_mode_bwd: the workspace must be 16-byte aligned and hold at least one workgroup's sums (%zu bytes)", part_bytes);
+  ALPRO_CHECK(!emit_out || emit_dtype == ALPRO_F32 || emit_dtype == ALPRO_BF16 || emit_dtype == ALPRO_F16, "alpro_vit_final_pool_mode_bwd: bad emit_dtype %d", emit_dtype);
+  ALPRO_CHECK(!emit_scale || emit_scale_group > 0, "alpro_vit_final_pool_mode_bwd: emit_scale_group must be > 0");
+  EmitArgs em;
+  em.out = emit_out; em.mode = emit_out ? ALPRO_EMIT_ROWS : ALPRO_EMIT_NONE; em.p0 = T; em.p1 = N; em.scale = emit_scale; em.group = emit_scale_group;
+  em.drop_p = 0.f; em.drop_seed = 0u; em.colsum_pre = nullptr; em.extra_cls = 0;
+  const int cap = get_option(OPT_LN_GRID);   // the grid plan of alpro_layernorm_bwd: 8 rows per wave at least, 2048 workgroups at most
+  int nblk = grid_for(rows, 4 * 8, cap > 0 ? cap : 256 * 8);
+  if (workspace) nblk = (int)std::min<size_t>((size_t)nblk, workspace_bytes / part_bytes);
+  const dim3 grid(nblk), blk(256);
+  float* part = (float*)workspace;
+  hipStream_t st = (hipStream_t)stream;
+#define ALPRO_FPB(TE, M) hipLaunchKernelGGL((vit_final_pool_bwd_kernel<TE, M>), grid, blk, 0, st, dout, x, gamma, eps, dx, dgamma, dbeta, rows, T, N, em, part)
+#define ALPRO_FPB_MODES(TE) \
+  do { if (mode == ALPRO_POOL_TEMPORAL) ALPRO_FPB(TE, ALPRO_POOL_TEMPORAL); else if (mode == ALPRO_POOL_SPATIAL) ALPRO_FPB(TE, ALPRO_POOL_SPATIAL); else ALPRO_FPB(TE, ALPRO_POOL_NONE); } while (0)
+  if (emit_out && emit_dtype == ALPRO_BF16) ALPRO_FPB_MODES(bf16_t);
+  else if (emit_out && emit_dtype == ALPRO_F16) ALPRO_FPB_MODES(f16_t);
+  else ALPRO_FPB_MODES(float);
+#undef ALPRO_FPB_MODES
+#undef ALPRO_FPB
+  if (part) hipLaunchKernelGGL(colsum_reduce_kernel, dim3(LN_D / 32, 2), dim3(1024), 0, st, part, nblk, 2, dgamma, dbeta, (float*)nullptr);
+  return check_launch("alpro_vit_final_pool_mode_bwd");
 }
 
 extern "C" int alpro_gather_cast(const float* src, int64_t ld, void* out, int dtype, int rows, int D, int map_mode, int map_p0, int map_p1,

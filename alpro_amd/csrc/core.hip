@@ -1,5 +1,6 @@
 // Forward row kernels and their entry points: casts, clip preparation, patchify, CLS mean, the sequence gather, and every kernel that works on
-// 768-wide rows one wave at a time (LayerNorm, residual add + LayerNorm, final-norm temporal pooling, BERT embeddings; helpers: row768.hpp).
+// 768-wide rows one wave at a time (LayerNorm, residual add + LayerNorm, final norm + temporal / spatial / per-frame pooling, BERT embeddings;
+// helpers: row768.hpp).
 // All are HBM-bound, 16-byte accesses.  The library's host state (errors, options, scheduler slots) is runtime.hip.
 #include "common.hpp"
 #include "row768.hpp"
@@ -296,6 +297,59 @@ __global__ __launch_bounds__(256) void vit_final_pool_kernel(const float* __rest
   if (out_t) ln_store<T>(out_t + wave * LN_D, lane, acc);
 }
 
+// final norm + spatial mean pool (ALPRO_POOL_SPATIAL): out row (b, 0) = LN(x[b,0]); (b, 1+t) = mean_n LN(x[b, 1+n*T+t]).  A frame's N token
+// rows lie T rows apart, so ONE workgroup of POOL_WAVES waves owns an output row: wave w normalises the patches n = w, w + POOL_WAVES, ... (whole
+// 3 KB rows, two per trip: both rows' loads are out before either row's wave reductions) and sums them in ascending n; wave 0 then adds the
+// POOL_WAVES partial sums in ascending w.  The order of the fp32 additions is a function of N and this constant alone -- no atomics, nothing
+// depends on the launch.  (The third mode, ALPRO_POOL_NONE, is layernorm_fwd_kernel under the FRAME_TOKENS row map.)
+constexpr int POOL_WAVES = 8;
+template <typename T>
+__global__ __launch_bounds__(POOL_WAVES * 64) void vit_final_pool_spatial_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
+                                                                                 const float* __restrict__ beta, float eps, float* __restrict__ out32,
+                                                                                 T* __restrict__ out_t, int Tn, int N) {
+  __shared__ float red[POOL_WAVES][LN_D];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int64_t o = blockIdx.x;   // output row b * (1 + T) + j
+  const int64_t b = o / (Tn + 1);
+  const int j = (int)(o - b * (Tn + 1));
+  const float* base = x + b * (1 + (int64_t)N * Tn) * LN_D;
+  const int cnt = j == 0 ? 1 : N;
+  auto row = [&](int n) { return j == 0 ? base : base + (1 + (int64_t)n * Tn + (j - 1)) * LN_D; };
+  float acc[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) acc[i] = 0.f;
+  for (int n = w; n < cnt; n += 2 * POOL_WAVES) {
+    const bool has2 = n + POOL_WAVES < cnt;
+    float v[12], v2[12], mean, rstd;
+    ln_load_nt(row(n), lane, v);
+    ln_load_nt(row(has2 ? n + POOL_WAVES : n), lane, v2);
+    ln_stats(v, eps, mean, rstd);
+    ln_affine(v, mean, rstd, gamma, beta, lane);
+#pragma unroll
+    for (int i = 0; i < 12; ++i) acc[i] += v[i];
+    if (has2) {
+      ln_stats(v2, eps, mean, rstd);
+      ln_affine(v2, mean, rstd, gamma, beta, lane);
+#pragma unroll
+      for (int i = 0; i < 12; ++i) acc[i] += v2[i];
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 12; ++i) red[w][row_col(lane, i)] = acc[i];
+  __syncthreads();
+  if (w != 0) return;
+  const float inv = 1.0f / (float)cnt;
+#pragma unroll
+  for (int i = 0; i < 12; ++i) {
+    float s = red[0][row_col(lane, i)];
+#pragma unroll
+    for (int k = 1; k < POOL_WAVES; ++k) s += red[k][row_col(lane, i)];
+    acc[i] = s * inv;
+  }
+  ln_store<float>(out32 + o * LN_D, lane, acc);
+  if (out_t) ln_store<T>(out_t + o * LN_D, lane, acc);
+}
+
 // BERT embeddings: word[id] + type0 + pos[l] -> LN
 template <typename T>
 __global__ __launch_bounds__(256) void bert_embed_kernel(const int64_t* __restrict__ ids, const float* __restrict__ word,
@@ -525,6 +579,30 @@ extern "C" int alpro_vit_final_pool(const float* x, const float* gamma, const fl
   const int64_t total = (int64_t)B * (N + 1);
   ALPRO_DISPATCH_DTYPE(dtype, T_, hipLaunchKernelGGL(vit_final_pool_kernel<T_>, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, eps, out32, (T_*)out_t, B, T, N));
   return check_launch("alpro_vit_final_pool");
+}
+
+extern "C" int alpro_vit_final_pool_mode(const float* x, const float* gamma, const float* beta, float eps, float* out32, void* out_t, int dtype,
+                                         int mode, int64_t rows, int B, int T, int N, int D, void* stream) {
+  ALPRO_CHECK(x && gamma && beta && out32 && B > 0 && T > 0 && N > 0, "alpro_vit_final_pool_mode: bad args");
+  ALPRO_CHECK(mode >= ALPRO_POOL_TEMPORAL && mode <= ALPRO_POOL_NONE, "alpro_vit_final_pool_mode: bad mode %d (ALPRO_POOL_TEMPORAL / _SPATIAL / _NONE)", mode);
+  ALPRO_CHECK(D == LN_D, "alpro_vit_final_pool_mode: D=%d unsupported (hidden size is 768 on this path)", D);
+  ALPRO_CHECK(rows == (int64_t)B * (1 + (int64_t)N * T), "alpro_vit_final_pool_mode: rows=%lld is not B * (1 + N * T) = %d * (1 + %d * %d)", (long long)rows, B, N, T);
+  ALPRO_CHECK(dtype == ALPRO_F32 || dtype == ALPRO_BF16 || dtype == ALPRO_F16, "alpro_vit_final_pool_mode: bad dtype %d", dtype);
+  ALPRO_CHECK(dtype != ALPRO_F32 || !out_t, "alpro_vit_final_pool_mode: out32 already is the fp32 output (pass out_t = NULL)");
+  if (mode == ALPRO_POOL_TEMPORAL) return alpro_vit_final_pool(x, gamma, beta, eps, out32, out_t, dtype, B, T, N, D, stream);
+  hipStream_t st = (hipStream_t)stream;
+  if (mode == ALPRO_POOL_SPATIAL) {
+    const int64_t out_rows = (int64_t)B * (1 + T);
+    ALPRO_CHECK(out_rows <= 0x7fffffff, "alpro_vit_final_pool_mode: %lld output rows exceed the grid", (long long)out_rows);
+    ALPRO_DISPATCH_DTYPE(dtype, T_, hipLaunchKernelGGL(vit_final_pool_spatial_kernel<T_>, dim3((unsigned)out_rows), dim3(POOL_WAVES * 64), 0, st, x, gamma, beta, eps, out32, (T_*)out_t, T, N));
+  } else {  // every patch of every frame behind the clip's CLS token: the FRAME_TOKENS gather of the spatial attention's input
+    const int64_t out_rows = (int64_t)B * T * (N + 1);
+    const dim3 grid(grid_for(out_rows, 4, 256 * 32)), blk(256);
+    float* no_stats = nullptr;
+    if (!out_t) hipLaunchKernelGGL(layernorm_fwd_kernel<float>, grid, blk, 0, st, x, (int64_t)LN_D, gamma, beta, eps, out32, (int64_t)LN_D, no_stats, no_stats, no_stats, out_rows, (int)ALPRO_MAP_FRAME_TOKENS, T, N);
+    else ALPRO_DISPATCH_DTYPE(dtype, T_, hipLaunchKernelGGL(layernorm_fwd_kernel<T_>, grid, blk, 0, st, x, (int64_t)LN_D, gamma, beta, eps, (T_*)out_t, (int64_t)LN_D, out32, no_stats, no_stats, out_rows, (int)ALPRO_MAP_FRAME_TOKENS, T, N));
+  }
+  return check_launch("alpro_vit_final_pool_mode");
 }
 
 extern "C" int alpro_bert_embed_fwd(const int64_t* ids, const float* word, const float* pos, const float* type0,

@@ -17,6 +17,7 @@ POOL_MODES = {"mean": 0, "max": 1, "lse": 2}   # alpro_clip_pool (run_video_qa.p
 MAP_IDENTITY, MAP_SKIP_CLS, MAP_FRAME_TOKENS, MAP_PATCH_EMBED = 0, 1, 2, 3
 ADD_IDENTITY, ADD_PRE_SPATIAL, ADD_PRE_MLP, ADD_PRE_TEMPORAL = 0, 1, 2, 3
 EMIT_NONE, EMIT_ROWS, EMIT_FRAME, EMIT_SKIP_CLS = 0, 1, 2, 3
+POOL_TEMPORAL, POOL_SPATIAL, POOL_NONE = 0, 1, 2   # ALPRO_POOL_*: the pooling modes of TimeSformer.forward_features (alpro_vit_final_pool_mode)
 
 _TORCH_DTYPE = {F32: torch.float32, BF16: torch.bfloat16, F16: torch.float16}
 _CODE = {v: k for k, v in _TORCH_DTYPE.items()}
@@ -26,7 +27,8 @@ EXPORTS = ["alpro_hip_last_error", "alpro_hip_abi_version", "alpro_hip_set_optio
            "alpro_vit_final_pool", "alpro_bert_embed_fwd", "alpro_cast_from_f32", "alpro_attn_bwd", "alpro_attn_temporal_bwd",
            "alpro_layernorm_bwd", "alpro_transpose", "alpro_transpose_batch", "alpro_gelu_bwd", "alpro_cls_mean_bwd", "alpro_scatter_add_rows", "alpro_gather_cast", "alpro_sumsq", "alpro_adamw_step", "alpro_gemm_tn_acc", "alpro_gemm_tn_acc_ws", "alpro_gemm_tn_workspace_bytes", "alpro_gemm_tn_ranges", "alpro_colsum_acc", "alpro_softmax_xent", "alpro_vtc_loss_fwd", "alpro_vtc_loss_bwd", "alpro_prepare_clips", "alpro_loss_scale_update", "alpro_add_layernorm_fwd", "alpro_layernorm_bwd_emit", "alpro_gemm_batch", "alpro_tproj_small", "alpro_attn_cls_fwd", "alpro_gemm_rows_f32", "alpro_gather_seq_fwd", "alpro_gather_seq_bwd", "alpro_scatter_add_rows_ordered",
            "alpro_hip_sched_workspace_bytes", "alpro_hip_set_sched_workspace", "alpro_hip_release_stream", "alpro_gemm_qkv_tattn", "alpro_add_layernorm_pre_mlp2", "alpro_adamw_step_lp",
-           "alpro_gemm_rows_f32_relu_mask", "alpro_clip_pool", "alpro_adamw_step_groups", "alpro_attn_temporal_fwd_drop", "alpro_attn_temporal_bwd_drop"]
+           "alpro_gemm_rows_f32_relu_mask", "alpro_clip_pool", "alpro_adamw_step_groups", "alpro_attn_temporal_fwd_drop", "alpro_attn_temporal_bwd_drop",
+           "alpro_vit_final_pool_mode", "alpro_vit_final_pool_mode_bwd"]
 
 
 class GemmDesc(ctypes.Structure):
@@ -131,6 +133,8 @@ def load():
     lib.alpro_patchify.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
     lib.alpro_cls_mean_residual.argtypes = [vp, i64, vp, vp, i64, i32, i32, i32, vp]
     lib.alpro_vit_final_pool.argtypes = [vp, vp, vp, f32, vp, vp, i32, i32, i32, i32, i32, vp]
+    lib.alpro_vit_final_pool_mode.argtypes = [vp, vp, vp, f32, vp, vp, i32, i32, i64, i32, i32, i32, i32, vp]
+    lib.alpro_vit_final_pool_mode_bwd.argtypes = [vp, vp, vp, f32, vp, vp, vp, i32, i64, i32, i32, i32, i32, vp, i32, vp, i32, vp, ctypes.c_size_t, vp]
     lib.alpro_add_layernorm_pre_mlp2.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, f32, vp, i64, i32, i32, i32, vp]
     lib.alpro_bert_embed_fwd.argtypes = [vp, vp, vp, vp, vp, vp, f32, vp, vp, i32, vp, vp, i32, i32, i32, f32, u32, vp]
     lib.alpro_cast_from_f32.argtypes = [vp, vp, i32, i64, vp]
@@ -753,6 +757,55 @@ def vit_final_pool(x, gamma, beta, eps, B, T, N, dtype):
     _check(lib.alpro_vit_final_pool(_ptr(x), _ptr(gamma), _ptr(beta), eps, _ptr(out32), _ptr(out_t), _CODE[dtype], B, T, N, D, _stream()),
            "alpro_vit_final_pool")
     return out32, (out_t if out_t is not None else out32)
+
+
+def _pool_out_shape(mode, B, T, N, D):
+    if mode not in (POOL_TEMPORAL, POOL_SPATIAL, POOL_NONE):
+        raise RuntimeError("final pool: bad mode %r (POOL_TEMPORAL / POOL_SPATIAL / POOL_NONE)" % (mode,))
+    return {POOL_TEMPORAL: (B, 1 + N, D), POOL_SPATIAL: (B, 1 + T, D), POOL_NONE: (B, T, 1 + N, D)}[mode]
+
+
+def vit_final_pool_mode(x, gamma, beta, eps, B, T, N, dtype, mode):
+    """Final LayerNorm + the pooling `mode` of TimeSformer.forward_features in one pass (alpro_vit_final_pool_mode): x (B, 1 + N*T, 768) fp32 ->
+    (out32, out in dtype) of shape (B, 1+N, 768) [POOL_TEMPORAL], (B, 1+T, 768) [POOL_SPATIAL] or (B, T, 1+N, 768) [POOL_NONE]."""
+    lib = load()
+    D = x.shape[-1]
+    shape = _pool_out_shape(mode, B, T, N, D)
+    _dev(x, torch.float32)
+    if gamma.numel() != D or beta.numel() != D:
+        raise RuntimeError("vit_final_pool_mode: gamma / beta hold %d / %d elements, not %d" % (gamma.numel(), beta.numel(), D))
+    out32 = torch.empty(shape, dtype=torch.float32, device=x.device)
+    out_t = torch.empty(shape, dtype=dtype, device=x.device) if dtype != torch.float32 else None
+    _check(lib.alpro_vit_final_pool_mode(_ptr(x), _ptr(_dev(gamma, torch.float32)), _ptr(_dev(beta, torch.float32)), eps, _ptr(out32), _ptr(out_t),
+                                         _CODE[dtype], mode, x.numel() // D, B, T, N, D, _stream()), "alpro_vit_final_pool_mode")
+    return out32, (out_t if out_t is not None else out32)
+
+
+def vit_final_pool_mode_bwd(dout, x, gamma, eps, dgamma, dbeta, B, T, N, mode, emit=None):
+    """Backward of vit_final_pool_mode (alpro_vit_final_pool_mode_bwd): dout fp32 in the forward's output shape, x the forward's input;
+    returns dx (fp32, x's shape), accumulates dgamma / dbeta (fp32, pre-initialised).  emit: None, or dict(dtype=, scale=<fp32 row scales or
+    None>, group=) -- the rows of dx also leave as the (rows, 768) operand dx[r] * scale[r // group] in `dtype`; then returns (dx, operand)."""
+    lib = load()
+    _dev(dout, torch.float32); _dev(x, torch.float32); _dev(dgamma, torch.float32); _dev(dbeta, torch.float32)
+    D = x.shape[-1]
+    rows = x.numel() // D
+    if tuple(dout.shape) != _pool_out_shape(mode, B, T, N, D):
+        raise RuntimeError("vit_final_pool_mode_bwd: dout is %s, mode %d at B=%d T=%d N=%d needs %s" % (tuple(dout.shape), mode, B, T, N, _pool_out_shape(mode, B, T, N, D)))
+    if gamma.numel() != D or dgamma.numel() != D or dbeta.numel() != D:
+        raise RuntimeError("vit_final_pool_mode_bwd: gamma / dgamma / dbeta hold %d / %d / %d elements, not %d" % (gamma.numel(), dgamma.numel(), dbeta.numel(), D))
+    dx = torch.empty_like(x)
+    out = sc = None
+    group = 1
+    if emit is not None:
+        out = torch.empty((rows, D), dtype=emit["dtype"], device=x.device)
+        sc, group = emit.get("scale"), emit.get("group", 1)
+        if sc is not None and (_dev(sc, torch.float32).numel() * group < rows or group <= 0):
+            raise RuntimeError("vit_final_pool_mode_bwd: %d row scales for groups of %d rows do not cover %d rows" % (sc.numel(), group, rows))
+    ws, wsb = _reduce_ws(x.device)
+    _check(lib.alpro_vit_final_pool_mode_bwd(_ptr(dout), _ptr(x), _ptr(_dev(gamma, torch.float32)), eps, _ptr(dx), _ptr(dgamma), _ptr(dbeta), mode, rows, B, T, N, D,
+                                             _ptr(out), _CODE[out.dtype] if out is not None else F32, _ptr(sc), group, ws, wsb, _stream()),
+           "alpro_vit_final_pool_mode_bwd")
+    return dx if emit is None else (dx, out)
 
 
 def bert_embed(ids, word, pos, type_emb, gamma, beta, eps, dtype, stats=False, drop_p=0.0, drop_seed=0):

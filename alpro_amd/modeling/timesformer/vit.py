@@ -905,17 +905,35 @@ class TimeSformer(nn.Module):
         self.model.default_cfg = default_cfgs['vit_base_patch' + str(self.patch_size) + '_224']
         self.num_patches = (self.img_size // self.patch_size) * (self.img_size // self.patch_size)
 
+    POOLING = {'temporal': hip.POOL_TEMPORAL, 'spatial': hip.POOL_SPATIAL, 'none': hip.POOL_NONE}   # vit.py:489
+
     def forward_features(self, x, return_all_tokens=True, pooling='temporal'):
-        """x: (b, c, t, h, w) -> (b, 1 + h*w/256, 768): final LayerNorm fused with the temporal mean pool.
+        """x: (b, c, t, h, w); the final LayerNorm fused with the pooling (vit.py:475-503), n = h*w/256 patches per frame:
+          'temporal' -> (b, 1 + n, 768)     CLS, then every patch averaged over the frames
+          'spatial'  -> (b, 1 + t, 768)     CLS, then every frame averaged over its patches
+          'none'     -> (b, t, 1 + n, 768)  every patch of every frame, the clip's CLS token in front of each frame
+        The reference reshapes the tokens by the CONFIG's img_size / num_frm (vit.py:481-487), so an input of another geometry raises there; here
+        it raises too in the two frame-resolved modes (the temporal mode keeps taking the resampled geometries the ALPRO models feed it).
         With autograd enabled the whole encoder is one autograd node with a hand-written backward."""
-        assert pooling == 'temporal' and return_all_tokens, "ALPRO only calls forward_features(return_all_tokens=True) with temporal pooling"
+        assert return_all_tokens, "forward_features(return_all_tokens=False) is not supported (the reference fails on it: vit.py:484 indexes the 2-D CLS tensor with three subscripts)"
+        assert pooling in ['temporal', 'spatial', 'none'], 'Invalid pooling type {}'.format(pooling)
+        mode = self.POOLING[pooling]
+        if mode != hip.POOL_TEMPORAL:
+            G, (t, h, w) = self.img_size // self.patch_size, x.shape[2:]
+            if (t, h // self.patch_size, w // self.patch_size) != (self.num_frames, G, G):
+                raise RuntimeError("forward_features(pooling=%r): the input has %d frames of %d x %d patches, the config (num_frm=%d, img_size=%d) says %d frames of "
+                                   "%d x %d -- the reference's rearrange (vit.py:487) fails on this input too" % (pooling, t, h // self.patch_size, w // self.patch_size,
+                                                                                                               self.num_frames, self.img_size, self.num_frames, G, G))
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            return tr.run_anchored(_VisualRun(self), [x], list(self.parameters()))
+            return tr.run_anchored(_VisualRun(self, mode), [x], list(self.parameters()))
         m = self.model
         B = x.shape[0]
         tok, T, W, N = m._embed(x)
         tok = run_blocks(m.blocks, tok, B, T, W)
-        out32, _ = hip.vit_final_pool(tok, m.norm.weight, m.norm.bias, VIT_EPS, B, T, N, torch.float32)
+        if mode == hip.POOL_TEMPORAL:
+            out32, _ = hip.vit_final_pool(tok, m.norm.weight, m.norm.bias, VIT_EPS, B, T, N, torch.float32)
+        else:
+            out32, _ = hip.vit_final_pool_mode(tok, m.norm.weight, m.norm.bias, VIT_EPS, B, T, N, torch.float32, mode)
         return out32
 
     def forward_cls(self, x):
@@ -945,8 +963,8 @@ class TimeSformer(nn.Module):
 class _VisualRun:
     """Forward/backward of the whole visual encoder for tr.Anchor (alpro_models.py:186-194 under autograd)."""
 
-    def __init__(self, enc):
-        self.enc = enc
+    def __init__(self, enc, mode=hip.POOL_TEMPORAL):
+        self.enc, self.mode = enc, mode   # mode: the pooling behind the final norm (hip.POOL_*)
 
     def forward(self, x):
         m = self.enc.model
@@ -962,23 +980,30 @@ class _VisualRun:
             self.saved.append(sv)
         _ClsSide.join(tok.device)
         self.tok = tok
-        out32, _ = hip.vit_final_pool(tok, m.norm.weight, m.norm.bias, VIT_EPS, B, T, N, torch.float32)
+        if self.mode == hip.POOL_TEMPORAL:
+            out32, _ = hip.vit_final_pool(tok, m.norm.weight, m.norm.bias, VIT_EPS, B, T, N, torch.float32)
+        else:
+            out32, _ = hip.vit_final_pool_mode(tok, m.norm.weight, m.norm.bias, VIT_EPS, B, T, N, torch.float32, self.mode)
         return out32
 
     def backward(self, dout):
         m = self.enc.model
         B, T, N = self.dims
         D = m.embed_dim
-        # final norm + temporal mean pool (vit.py:372,484-492): every frame token receives dout / T, the CLS token dout
-        dy = torch.empty((B, 1 + N * T, D), dtype=torch.float32, device=dout.device)
-        dy[:, 0] = dout[:, 0]
-        torch.mul(dout[:, 1:].unsqueeze(2).expand(B, N, T, D), 1.0 / T, out=dy[:, 1:].view(B, N, T, D))  # one broadcast pass (was mul + repeat_interleave + copy)
-        dtok = torch.empty_like(dy)
         g, b_ = tr.grad_buffer(m.norm.weight, zero=True)[0], tr.grad_buffer(m.norm.bias, zero=True)[0]
         S_ = 1 + N * T   # the final norm's backward emits the last block's MLP operand rows (its drop-path scale)
-        _, dz = hip.layernorm_bwd(dy.view(-1, D), self.tok, m.norm.weight, VIT_EPS, dtok, g, b_, accumulate=False,
-                                  emit=dict(mode=hip.EMIT_ROWS, rows=B * S_, dtype=self.saved[-1]["dt"], scale=self.saved[-1]["drop_m"], group=S_))
-        del dy
+        if self.mode == hip.POOL_TEMPORAL:
+            # final norm + temporal mean pool (vit.py:372,484-492): every frame token receives dout / T, the CLS token dout
+            dy = torch.empty((B, 1 + N * T, D), dtype=torch.float32, device=dout.device)
+            dy[:, 0] = dout[:, 0]
+            torch.mul(dout[:, 1:].unsqueeze(2).expand(B, N, T, D), 1.0 / T, out=dy[:, 1:].view(B, N, T, D))  # one broadcast pass (was mul + repeat_interleave + copy)
+            dtok = torch.empty_like(dy)
+            _, dz = hip.layernorm_bwd(dy.view(-1, D), self.tok, m.norm.weight, VIT_EPS, dtok, g, b_, accumulate=False,
+                                      emit=dict(mode=hip.EMIT_ROWS, rows=B * S_, dtype=self.saved[-1]["dt"], scale=self.saved[-1]["drop_m"], group=S_))
+            del dy
+        else:   # spatial / none (vit.py:493-499): dout is un-pooled inside the LayerNorm-backward pass itself, dy is never built
+            dtok, dz = hip.vit_final_pool_mode_bwd(dout, self.tok, m.norm.weight, VIT_EPS, g, b_, B, T, N, self.mode,
+                                                   emit=dict(dtype=self.saved[-1]["dt"], scale=self.saved[-1]["drop_m"], group=S_))
         bank = m.blocks[0]._bank()
         dt_run = self.saved[-1]["dt"]
         banked = bank is not None and dt_run != torch.float32 and all(sv["merged"] for sv in self.saved)

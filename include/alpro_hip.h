@@ -305,6 +305,25 @@ int alpro_cls_mean_residual(const float* x_in, int64_t ld_batch_in, const float*
 int alpro_vit_final_pool(const float* x, const float* gamma, const float* beta, float eps, float* out32,
                          void* out_t, int dtype, int B, int T, int N, int D, void* stream);
 
+/* The same tail for the three pooling modes of TimeSformer.forward_features (vit.py:475-503), y = LayerNorm(x), patch (n, t) at token row
+ * 1 + n*T + t of a clip (still ABI 22: additions only):
+ *   ALPRO_POOL_TEMPORAL  out (B, 1+N, D):    out[b, 0] = y[b, 0], out[b, 1+n] = mean_t y[b, 1+n*T+t]      (alpro_vit_final_pool itself)
+ *   ALPRO_POOL_SPATIAL   out (B, 1+T, D):    out[b, 0] = y[b, 0], out[b, 1+t] = mean_n y[b, 1+n*T+t]      (the sum over n in an order fixed by N)
+ *   ALPRO_POOL_NONE      out (B, T, 1+N, D): out[b, t, 0] = y[b, 0], out[b, t, 1+n] = y[b, 1+n*T+t]       (the ALPRO_MAP_FRAME_TOKENS gather)
+ * out32 fp32, always written; out_t: the same rows in the 16-bit `dtype`, or NULL.  rows = token rows of x, must equal B * (1 + N*T). */
+enum { ALPRO_POOL_TEMPORAL = 0, ALPRO_POOL_SPATIAL = 1, ALPRO_POOL_NONE = 2 };
+int alpro_vit_final_pool_mode(const float* x, const float* gamma, const float* beta, float eps, float* out32, void* out_t, int dtype,
+                              int mode, int64_t rows, int B, int T, int N, int D, void* stream);
+/* Its backward: dout (fp32, the shape of `out` above) is un-pooled inside the LayerNorm backward pass -- token row (n, t) of clip b takes
+ * dout[b, 1+n] / T, dout[b, 1+t] / N or dout[b, t, 1+n], the CLS row dout[b, 0] (NONE: sum_t dout[b, t, 0], t ascending) -- and
+ * dx (B, 1+N*T, D) fp32 is WRITTEN (every token row has one writer), dgamma / dbeta are ACCUMULATED: through per-workgroup partials in the
+ * reduction workspace and a fixed-order second kernel (>= 6144 bytes, 16-byte aligned; see alpro_layernorm_bwd), or with workspace = NULL by
+ * fp32 atomics.  emit_out != NULL: the finished rows also leave as out[r] = (emit_dtype) dx[r] * emit_scale[r / emit_scale_group]
+ * (emit_scale NULL = 1), the ALPRO_EMIT_ROWS operand of the last block's MLP GEMMs. */
+int alpro_vit_final_pool_mode_bwd(const float* dout, const float* x, const float* gamma, float eps, float* dx, float* dgamma, float* dbeta,
+                                  int mode, int64_t rows, int B, int T, int N, int D, void* emit_out, int emit_dtype, const float* emit_scale,
+                                  int emit_scale_group, void* workspace, size_t workspace_bytes, void* stream);
+
 /* BERT embeddings (xbert.py:186-213): word[ids] + type[0] + pos[l] -> LayerNorm -> y32 (+ y_t). */
 int alpro_bert_embed_fwd(const int64_t* ids, const float* word, const float* pos, const float* type0,
                          const float* gamma, const float* beta, float eps, float* y32, void* y_t, int dtype,
