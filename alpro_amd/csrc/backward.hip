@@ -82,8 +82,9 @@ struct EmitArgs {
   int extra_cls;             // ROWS mode after a SKIP_CLS-mapped LayerNorm: also emit the B CLS rows (final since the previous kernel)
 };
 
-// emit the finished gradient row `v` of token row r (see EmitArgs); cp accumulates the unscaled column sums (SKIP_CLS mode)
-template <typename T>
+// emit the finished gradient row `v` of token row r (see EmitArgs); cp accumulates the unscaled column sums (SKIP_CLS mode; CP = false:
+// nobody wants them -- the data-only LayerNorm backward -- and cp is left alone)
+template <typename T, bool CP = true>
 __device__ __forceinline__ void emit_row(const EmitArgs& e, int64_t r, int lane, float (&v)[12], float (&cp)[12]) {
   T* out = (T*)e.out;
   if (e.mode == ALPRO_EMIT_ROWS) {
@@ -111,140 +112,20 @@ __device__ __forceinline__ void emit_row(const EmitArgs& e, int64_t r, int lane,
   } else {  // SKIP_CLS
     if (k == 0) return;
     const int64_t o = r - b - 1;
+    if constexpr (CP) {
 #pragma unroll
-    for (int i = 0; i < 12; ++i) cp[i] += v[i];
+      for (int i = 0; i < 12; ++i) cp[i] += v[i];
+    }
     ln_store_scaled<T>(out + o * LN_D, lane, v, e.scale ? e.scale[o / e.group] : 1.0f);
   }
 }
 
-// dx[src(m)] += rstd * (dy*g - mean(dy*g) - xhat * mean(dy*g*xhat));  dgamma += dy*xhat;  dbeta += dy
-// T = storage type of dy, TE = storage type of the emitted operand rows (the compute dtype; dy itself may be the fp32 stream)
-template <typename T, typename TE>
-__global__ __launch_bounds__(256) void layernorm_bwd_kernel(const T* __restrict__ dy, int64_t ld_dy, const float* __restrict__ dy2,
-                                                            const float* __restrict__ x, int64_t ldx, const float* __restrict__ gamma, float eps,
-                                                            float* __restrict__ dx, int64_t ld_dx, int accumulate, float* __restrict__ dgamma,
-                                                            float* __restrict__ dbeta, int64_t rows, int mode, int p0, int p1, float drop_p,
-                                                            uint32_t drop_seed, const EmitArgs em, float* __restrict__ part, float* __restrict__ cls_ws) {
-  __shared__ float red[2][4][LN_D];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int64_t wave = (int64_t)blockIdx.x * 4 + w;
-  const int64_t nwaves = (int64_t)gridDim.x * 4;
-  float g[12], ag[12], ab[12], cp[12];
-  ln_load(gamma, lane, g);
-#pragma unroll
-  for (int i = 0; i < 12; ++i) ag[i] = ab[i] = cp[i] = 0.f;
-  // one row: loads, statistics, dgamma / dbeta terms; fin = its input-gradient row (not stored here)
-  auto row_grad = [&](int64_t m, int64_t srow, float (&fin)[12]) {
-    float xv[12], d[12];
-    ln_load_nt(x + srow * ldx, lane, xv);
-    ln_load_t<T>(dy + m * ld_dy, lane, d);
-    if (dy2) {  // second gradient stream on the same LN output (fp32 copy consumed as a residual)
-      float d2[12];
-      ln_load_nt(dy2 + m * LN_D, lane, d2);
-#pragma unroll
-      for (int i = 0; i < 12; ++i) d[i] += d2[i];
-    }
-    if (drop_seed) {  // gradient through the dropout applied to this LayerNorm's output
-      const uint32_t th = drop_thresh24(drop_p);
-      const float ks = 1.0f / (1.0f - drop_p);
-#pragma unroll
-      for (int i = 0; i < 12; ++i) d[i] = row_drop_keep(drop_seed, m, lane, i, th) ? d[i] * ks : 0.f;
-    }
-    float mean, rstd;
-    ln_stats(xv, eps, mean, rstd);
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int i = 0; i < 12; ++i) {
-      xv[i] = (xv[i] - mean) * rstd;  // xhat
-      ab[i] += d[i];
-      ag[i] += d[i] * xv[i];
-      d[i] *= g[i];             // dy * gamma
-      s1 += d[i];
-      s2 += d[i] * xv[i];
-    }
-    s1 = wave_sum(s1) * (1.0f / LN_D);
-    s2 = wave_sum(s2) * (1.0f / LN_D);
-#pragma unroll
-    for (int i = 0; i < 12; ++i) fin[i] = rstd * (d[i] - s1 - xv[i] * s2);
-  };
-  for (int64_t m = wave; m < rows + em.extra_cls; m += nwaves) {
-    if (m >= rows) {  // cast-only rows: the CLS rows a SKIP_CLS-mapped LayerNorm does not touch (their gradient is already final)
-      const int64_t r = (m - rows) * (1 + (int64_t)em.p1 * em.p0);
-      float v[12];
-      ln_load_nt(dx + r * ld_dx, lane, v);
-      emit_row<TE>(em, r, lane, v, cp);
-      continue;
-    }
-    const SrcRow src = ln_src_row(mode, p0, p1, m);
-    // round 6: the row of dx that the result is added to is fetched WITH the row's x / dy (it used to be read behind the four dependent wave
-    // reductions: a second exposed memory latency per row)
-    f32x4 cin[3];
-    const bool acc_here = accumulate && !src.shared;
-    if (acc_here) {
-      const float* o = dx + src.row * ld_dx;
-#pragma unroll
-      for (int i = 0; i < 3; ++i) cin[i] = __builtin_nontemporal_load((const f32x4*)(o + i * 256 + lane * 4));
-    }
-    float fin[12];  // the finished gradient row
-    row_grad(m, src.row, fin);
-    if (src.shared) {
-      // FRAME_TOKENS: the clip's CLS row receives one term per frame.  With a workspace the term of frame copy m / (N + 1) = b * T + t is
-      // parked in cls_ws[b * T + t] and cls_rows_reduce_kernel adds the T terms of a clip in frame order (one writer per row, fixed order);
-      // without one, fp32 atomics straight into the row (rounds 1-3: run-to-run differences in the last bit)
-      if (cls_ws) {
-        float* o = cls_ws + (m / (p1 + 1)) * LN_D;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) *(float4*)(o + i * 256 + lane * 4) = make_float4(fin[4 * i], fin[4 * i + 1], fin[4 * i + 2], fin[4 * i + 3]);
-      } else {
-        float* o = dx + src.row * ld_dx;
-#pragma unroll
-        for (int i = 0; i < 12; ++i) atomicAdd(o + row_col(lane, i), fin[i]);
-      }
-      continue;
-    }
-    float* o = dx + src.row * ld_dx;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      float* p = o + i * 256 + lane * 4;
-      if (acc_here) {
-        fin[4 * i] += cin[i].x; fin[4 * i + 1] += cin[i].y; fin[4 * i + 2] += cin[i].z; fin[4 * i + 3] += cin[i].w;
-      }
-      __builtin_nontemporal_store(f32x4{fin[4 * i], fin[4 * i + 1], fin[4 * i + 2], fin[4 * i + 3]}, (f32x4*)p);
-    }
-    if (em.mode != ALPRO_EMIT_NONE) emit_row<TE>(em, src.row, lane, fin, cp);
-  }
-  // block reduction of dgamma / dbeta (and the emit's column sums).  part != nullptr: this workgroup's sums go to its slot of the caller's
-  // workspace -- part[block][3][768] -- and colsum_reduce_kernel adds the slots in a fixed order (bit-reproducible, the default since
-  // round 4); part == nullptr: one fp32 atomic per column per workgroup straight into the gradients (no workspace, order varies)
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      red[0][w][i * 256 + lane * 4 + e] = ag[4 * i + e];
-      red[1][w][i * 256 + lane * 4 + e] = ab[4 * i + e];
-    }
-  __syncthreads();
-  float* slot = part ? part + (int64_t)blockIdx.x * (3 * LN_D) : nullptr;
-  for (int c = threadIdx.x; c < LN_D; c += 256) {
-    const float sg = red[0][0][c] + red[0][1][c] + red[0][2][c] + red[0][3][c];
-    const float sb = red[1][0][c] + red[1][1][c] + red[1][2][c] + red[1][3][c];
-    if (slot) { slot[c] = sg; slot[LN_D + c] = sb; }
-    else { atomicAdd(dgamma + c, sg); atomicAdd(dbeta + c, sb); }
-  }
-  if (em.colsum_pre) {  // bias gradient of the Linear whose output gradient the emitted rows are (before the row scale)
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) red[0][w][i * 256 + lane * 4 + e] = cp[4 * i + e];
-    __syncthreads();
-    for (int c = threadIdx.x; c < LN_D; c += 256) {
-      const float sc = red[0][0][c] + red[0][1][c] + red[0][2][c] + red[0][3][c];
-      if (slot) slot[2 * LN_D + c] = sc;
-      else atomicAdd(em.colsum_pre + c, sc);
-    }
-  }
-}
+#define ALPRO_LN_DATA 0
+#include "layernorm_bwd_kernel.hpp"
+#undef ALPRO_LN_DATA
+#define ALPRO_LN_DATA 1
+#include "layernorm_bwd_kernel.hpp"
+#undef ALPRO_LN_DATA
 
 // dst_k[c] += sum over workgroup slots p of part[p][nslots][768] for the column sums k = 0 .. gridDim.y-1: ONE workgroup per (32 columns, k)
 // -- 8 float4 column lanes x 128 slices of slots.  Slice s adds slots s, s + 128, ... in ascending order; then 8 x 8 lanes add 16 slice sums
@@ -641,6 +522,58 @@ __global__ __launch_bounds__(256) void tproj_small_kernel(const alpro_tproj_job_
   }
 }
 
+// ---- colsum[n] += sum_m A[m, n] in the order of alpro_gemm_tn_acc_ws's bias gradient: the column sums of a Linear whose WEIGHT is frozen ------
+// (requires_grad == False) while its bias is trained, so the dW GEMM that used to produce them does not run.  The sums must keep the bits that
+// GEMM gives them (the all-trainable step is the oracle of the frozen-parameter tests), so this kernel restates its additions, not its speed:
+//   * the weight-gradient GEMM cuts the tokens into R ranges of `per` 32-token stages; the ceil(K / 256) k-tiles that share a dY column panel take
+//     turns, k-tile tk summing the stages with stage % tk_cnt == tk: one partial per (range, k-tile) = "set", set = range * tk_cnt + tk;
+//   * inside a stage a lane owns one column and one token half g: tokens ks*16 + 4g + {0..3} and ks*16 + 8 + 4g + {0..3} for ks = 0, 1 (frag8 of
+//     gemm_tn.hip), added as ((f0+f1)+(f2+f3))+((f4+f5)+(f6+f7)) onto the running sum, ks = 0 first; the two halves meet at the end (g = 0 + g = 1);
+//     rows past M count as zeros;
+//   * colsum_tn_reduce_kernel adds the sets as tn_reduce_kernel does: eight interleaved chains (set p, p + 8, ...) and a fixed tree over the eight.
+// One wave per (set, 32 columns); every load is a 2-byte element of a 64-byte row segment -- a fraction of HBM speed, on a tensor the skipped GEMM
+// would have read anyway.
+template <typename T>
+__global__ __launch_bounds__(256) void colsum_tn_kernel(const T* __restrict__ A, int64_t lda, int M, int N, int per, int tk_cnt, int total_steps,
+                                                        float* __restrict__ part, int npad) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int cg = blockIdx.x * 4 + w;
+  if (cg * 32 >= npad) return;
+  const int col = cg * 32 + (lane & 31), g = lane >> 5;
+  const int set = blockIdx.y, range = set / tk_cnt, tk = set - range * tk_cnt;
+  const int s0 = range * per, s1 = min(s0 + per, total_steps);
+  const bool cv = col < N;
+  float cs = 0.f;
+  for (int st = s0 + (tk - s0 % tk_cnt + tk_cnt) % tk_cnt; st < s1; st += tk_cnt) {
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      const int base = st * 32 + ks * 16 + 4 * g;
+      float f[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int m = base + (j & 3) + (j >> 2) * 8;
+        f[j] = (cv && m < M) ? to_f32(A[(int64_t)m * lda + col]) : 0.f;
+      }
+      cs += ((f[0] + f[1]) + (f[2] + f[3])) + ((f[4] + f[5]) + (f[6] + f[7]));
+    }
+  }
+  const float t = cs + __shfl_xor(cs, 32, 64);
+  if (lane < 32) part[(int64_t)set * npad + col] = t;
+}
+
+__global__ __launch_bounds__(256) void colsum_tn_reduce_kernel(const float* __restrict__ part, int sets, int npad, float* __restrict__ colsum, int N) {
+  const int n = blockIdx.x * 256 + threadIdx.x;
+  if (n >= N) return;
+  float r[8];
+#pragma unroll
+  for (int p = 0; p < 8; ++p) {
+    float t = 0.f;
+    for (int s = p; s < sets; s += 8) t += part[(int64_t)s * npad + n];
+    r[p] = t;
+  }
+  colsum[n] += ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+}
+
 inline int grid_for(int64_t work_items, int per_block, int cap) {
   int64_t g = (work_items + per_block - 1) / per_block;
   if (g < 1) g = 1;
@@ -686,7 +619,14 @@ extern "C" int alpro_layernorm_bwd_emit(const void* dy, int dy_dtype, int64_t ld
                                         int emit_dtype, int emit_mode, int emit_p0, int emit_p1, const float* emit_scale, int emit_scale_group, float emit_drop_p,
                                         uint32_t emit_drop_seed, float* emit_colsum_pre, int emit_extra_cls, void* workspace, size_t workspace_bytes,
                                         void* stream) {
-  ALPRO_CHECK(dy && x && gamma && dx && dgamma && dbeta && rows > 0, "alpro_layernorm_bwd: bad args");
+  ALPRO_CHECK(dy && x && gamma && dx && rows > 0, "alpro_layernorm_bwd: bad args");
+  // dgamma == dbeta == NULL: gamma and beta are frozen -- the data-only form (layernorm_bwd_data_kernel: the same dx and emitted rows, no column sums,
+  // no reduce launch).  The two come and go together, and a column sum somebody still wants (colsum_pre: the temporal_fc bias) takes the full kernel:
+  // the caller then hands over a throw-away dgamma / dbeta pair.
+  ALPRO_CHECK((dgamma != nullptr) == (dbeta != nullptr), "alpro_layernorm_bwd: dgamma and dbeta must both be given or both be NULL (got %s only); "
+              "pass a throw-away buffer for the one that is not wanted", dgamma ? "dgamma" : "dbeta");
+  const bool data_only = dgamma == nullptr;
+  ALPRO_CHECK(!data_only || !emit_colsum_pre, "alpro_layernorm_bwd_emit: colsum_pre needs the column-sum form of the kernel -- pass a throw-away dgamma / dbeta pair with it");
   ALPRO_CHECK(!workspace || (((uintptr_t)workspace % 16) == 0 && workspace_bytes >= LN_PART_BYTES), "alpro_layernorm_bwd: the workspace must be 16-byte aligned and hold at least one workgroup's sums (%d bytes)", LN_PART_BYTES);
   ALPRO_CHECK(D == LN_D, "alpro_layernorm_bwd: D=%d unsupported", D);
   ALPRO_CHECK(map_mode >= 0 && map_mode <= ALPRO_MAP_FRAME_TOKENS, "alpro_layernorm_bwd: bad map_mode %d", map_mode);
@@ -710,16 +650,18 @@ extern "C" int alpro_layernorm_bwd_emit(const void* dy, int dy_dtype, int64_t ld
   const bool frame = map_mode == ALPRO_MAP_FRAME_TOKENS;
   const size_t cls_bytes = frame ? (size_t)(rows / (map_p1 + 1)) * LN_D * sizeof(float) : 0;
   ALPRO_CHECK(!workspace || workspace_bytes >= cls_bytes + LN_PART_BYTES, "alpro_layernorm_bwd: the workspace must hold the CLS frame terms (%zu bytes) and at least one workgroup's sums", cls_bytes);
-  // workgroup count: 8 rows per wave at least, 2048 workgroups at most -- two 4-wave workgroups per CU are resident at a time (185 VGPRs), so
+  // workgroup count: 8 rows per wave at least, 2048 workgroups at most -- two 4-wave workgroups per CU are resident at a time (157 VGPRs, 24 KB LDS), so
   // that is 4 rounds; fewer, fatter workgroups measured slower (tools/ln_bwd_bench.py: 1024: +14 %, 512: +5 %; `ln_grid` overrides the cap)
   const int cap = get_option(OPT_LN_GRID);
   int nblk = grid_for(rows, 4 * 8, cap > 0 ? cap : 256 * 8);
-  if (workspace) nblk = (int)std::min<size_t>((size_t)nblk, (workspace_bytes - cls_bytes) / LN_PART_BYTES);
+  if (workspace && !data_only) nblk = (int)std::min<size_t>((size_t)nblk, (workspace_bytes - cls_bytes) / LN_PART_BYTES);
   const dim3 grid(nblk), blk(256);
-  float* part = (float*)workspace;
-  float* cls_ws = (workspace && frame) ? part + (size_t)nblk * 3 * LN_D : nullptr;
+  float* part = data_only ? nullptr : (float*)workspace;   // data-only: no partials; the CLS frame terms lie at the head of the workspace
+  float* cls_ws = (workspace && frame) ? (float*)workspace + (data_only ? 0 : (size_t)nblk * 3 * LN_D) : nullptr;
   hipStream_t st = (hipStream_t)stream;
-#define ALPRO_LNB(T, TE) hipLaunchKernelGGL((layernorm_bwd_kernel<T, TE>), grid, blk, 0, st, (const T*)dy, ld_dy, dy2, x, ldx, gamma, eps, dx, ld_dx, accumulate, dgamma, dbeta, (int64_t)rows, map_mode, map_p0, map_p1, drop_p, drop_seed, em, part, cls_ws)
+#define ALPRO_LNB(T, TE) \
+  do { if (data_only) ALPRO_LNB_K(layernorm_bwd_data_kernel, T, TE); else ALPRO_LNB_K(layernorm_bwd_kernel, T, TE); } while (0)
+#define ALPRO_LNB_K(KERNEL, T, TE) hipLaunchKernelGGL((KERNEL<T, TE>), grid, blk, 0, st, (const T*)dy, ld_dy, dy2, x, ldx, gamma, eps, dx, ld_dx, accumulate, dgamma, dbeta, (int64_t)rows, map_mode, map_p0, map_p1, drop_p, drop_seed, em, part, cls_ws)
   if (dy_dtype == ALPRO_F32 && emit_mode != ALPRO_EMIT_NONE && emit_dtype == ALPRO_BF16) ALPRO_LNB(float, bf16_t);
   else if (dy_dtype == ALPRO_F32 && emit_mode != ALPRO_EMIT_NONE && emit_dtype == ALPRO_F16) ALPRO_LNB(float, f16_t);
   else if (dy_dtype == ALPRO_F32) ALPRO_LNB(float, float);
@@ -727,6 +669,7 @@ extern "C" int alpro_layernorm_bwd_emit(const void* dy, int dy_dtype, int64_t ld
   else if (dy_dtype == ALPRO_F16) ALPRO_LNB(f16_t, f16_t);
   else { set_error("alpro_layernorm_bwd: bad dtype %d", dy_dtype); return ALPRO_ERR_INVALID; }
 #undef ALPRO_LNB
+#undef ALPRO_LNB_K
   if (part) hipLaunchKernelGGL(colsum_reduce_kernel, dim3(LN_D / 32, emit_colsum_pre ? 3 : 2), dim3(1024), 0, st, part, nblk, 3, dgamma, dbeta, emit_colsum_pre);
   if (cls_ws) hipLaunchKernelGGL(cls_rows_reduce_kernel, dim3(rows / (map_p1 + 1) / map_p0), dim3(192), 0, st, cls_ws, dx, ld_dx, map_p0, map_p1);
   return check_launch("alpro_layernorm_bwd");
@@ -793,6 +736,26 @@ extern "C" int alpro_gather_cast(const float* src, int64_t ld, void* out, int dt
     ALPRO_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((gather_cast_kernel<T, 4>), dim3(grid_for(rows, 8, 256 * 32)), dim3(256), 0, (hipStream_t)stream, src, ld, (T*)out, (int64_t)rows, map_mode, map_p0, map_p1, row_scale, row_scale_group, cls_scale, drop_p, drop_seed, colsum, colsum_pre, (float*)nullptr));
   }
   return check_launch("alpro_gather_cast");
+}
+
+extern "C" int alpro_colsum_tn(const void* A, int64_t lda, int dtype, int M, int N, int K, float* colsum, void* workspace, size_t workspace_bytes,
+                               void* stream) {
+  ALPRO_CHECK(A && colsum && M > 0 && N > 0 && K > 0, "alpro_colsum_tn: bad args");
+  ALPRO_CHECK(dtype == ALPRO_BF16 || dtype == ALPRO_F16, "alpro_colsum_tn: 16-bit rows only (it restates the 16-bit weight-gradient GEMM's bias gradient)");
+  ALPRO_CHECK(lda >= N, "alpro_colsum_tn: lda must cover N");
+  // the token-range plan of the weight-gradient GEMM this launch stands in for (workspace plan, this stream's CU budget)
+  const int ranges = alpro_gemm_tn_ranges(M, N, K, cu_budget((hipStream_t)stream));
+  const int total_steps = (M + 31) / 32, per = (total_steps + ranges - 1) / ranges, tk_cnt = (K + 255) / 256;
+  const int sets = ranges * tk_cnt, npad = (N + 31) / 32 * 32;
+  ALPRO_CHECK(workspace && ((uintptr_t)workspace % 16) == 0 && workspace_bytes >= (size_t)sets * npad * sizeof(float),
+              "alpro_colsum_tn: the workspace must be 16-byte aligned and hold %d partial sets of %d floats (%zu bytes)", sets, npad, (size_t)sets * npad * sizeof(float));
+  float* part = (float*)workspace;
+  const dim3 grid((npad / 32 + 3) / 4, sets);
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == ALPRO_BF16) hipLaunchKernelGGL(colsum_tn_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)A, lda, M, N, per, tk_cnt, total_steps, part, npad);
+  else hipLaunchKernelGGL(colsum_tn_kernel<f16_t>, grid, dim3(256), 0, st, (const f16_t*)A, lda, M, N, per, tk_cnt, total_steps, part, npad);
+  hipLaunchKernelGGL(colsum_tn_reduce_kernel, dim3((N + 255) / 256), dim3(256), 0, st, part, sets, npad, colsum, N);
+  return check_launch("alpro_colsum_tn");
 }
 
 extern "C" int alpro_tproj_small(const alpro_tproj_job_t* jobs_device, int njobs, int D, int mode, void* stream) {

@@ -25,7 +25,7 @@ _CODE = {v: k for k, v in _TORCH_DTYPE.items()}
 EXPORTS = ["alpro_hip_last_error", "alpro_hip_abi_version", "alpro_hip_set_option", "alpro_hip_set_stream_option", "alpro_gemm", "alpro_gemm_c2_tiled_rows", "alpro_layernorm_fwd",
            "alpro_attn_temporal_fwd", "alpro_attn_fwd", "alpro_patchify", "alpro_cls_mean_residual",
            "alpro_vit_final_pool", "alpro_bert_embed_fwd", "alpro_cast_from_f32", "alpro_attn_bwd", "alpro_attn_temporal_bwd",
-           "alpro_layernorm_bwd", "alpro_transpose", "alpro_transpose_batch", "alpro_gelu_bwd", "alpro_cls_mean_bwd", "alpro_scatter_add_rows", "alpro_gather_cast", "alpro_sumsq", "alpro_adamw_step", "alpro_gemm_tn_acc", "alpro_gemm_tn_acc_ws", "alpro_gemm_tn_workspace_bytes", "alpro_gemm_tn_ranges", "alpro_colsum_acc", "alpro_softmax_xent", "alpro_vtc_loss_fwd", "alpro_vtc_loss_bwd", "alpro_prepare_clips", "alpro_loss_scale_update", "alpro_add_layernorm_fwd", "alpro_layernorm_bwd_emit", "alpro_gemm_batch", "alpro_tproj_small", "alpro_attn_cls_fwd", "alpro_gemm_rows_f32", "alpro_gather_seq_fwd", "alpro_gather_seq_bwd", "alpro_scatter_add_rows_ordered",
+           "alpro_layernorm_bwd", "alpro_transpose", "alpro_transpose_batch", "alpro_gelu_bwd", "alpro_cls_mean_bwd", "alpro_scatter_add_rows", "alpro_gather_cast", "alpro_sumsq", "alpro_adamw_step", "alpro_gemm_tn_acc", "alpro_gemm_tn_acc_ws", "alpro_gemm_tn_workspace_bytes", "alpro_gemm_tn_ranges", "alpro_colsum_acc", "alpro_colsum_tn", "alpro_softmax_xent", "alpro_vtc_loss_fwd", "alpro_vtc_loss_bwd", "alpro_prepare_clips", "alpro_loss_scale_update", "alpro_add_layernorm_fwd", "alpro_layernorm_bwd_emit", "alpro_gemm_batch", "alpro_tproj_small", "alpro_attn_cls_fwd", "alpro_gemm_rows_f32", "alpro_gather_seq_fwd", "alpro_gather_seq_bwd", "alpro_scatter_add_rows_ordered",
            "alpro_hip_sched_workspace_bytes", "alpro_hip_set_sched_workspace", "alpro_hip_release_stream", "alpro_gemm_qkv_tattn", "alpro_add_layernorm_pre_mlp2", "alpro_adamw_step_lp",
            "alpro_gemm_rows_f32_relu_mask", "alpro_clip_pool", "alpro_adamw_step_groups", "alpro_attn_temporal_fwd_drop", "alpro_attn_temporal_bwd_drop",
            "alpro_vit_final_pool_mode", "alpro_vit_final_pool_mode_bwd"]
@@ -115,6 +115,7 @@ def load():
     lib.alpro_gemm_tn_workspace_bytes.restype = ctypes.c_size_t
     lib.alpro_gemm_tn_ranges.argtypes = [i32, i32, i32, i32]
     lib.alpro_colsum_acc.argtypes = [vp, i64, vp, i32, i32, i32, vp]
+    lib.alpro_colsum_tn.argtypes = [vp, i64, i32, i32, i32, i32, vp, vp, ctypes.c_size_t, vp]
     lib.alpro_transpose_batch.argtypes = [vp, i32, i32, i32, vp]
     lib.alpro_adamw_step.argtypes = [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, vp, f32, f32, vp, i32, i32, i32, vp]
     lib.alpro_adamw_step_lp.argtypes = [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, vp, f32, f32, vp, i32, i32, i32, vp, i32, vp]
@@ -471,14 +472,35 @@ def attn_bwd(qkv, out, dout, lse, batch, L, H, scale, key_bias=None, drop_p=0.0,
     return dqkv
 
 
-def layernorm_bwd(dy, x, gamma, eps, dx, dgamma, dbeta, rows=None, dy2=None, accumulate=True, map_mode=MAP_IDENTITY, map_p0=0, map_p1=0,
+_LN_THROWAWAY = {}
+
+
+def ln_throwaway_pair(device):
+    """(dgamma, dbeta) targets for a LayerNorm backward whose gamma and beta are frozen but which has to run the column-sum form of its
+    kernel all the same (a wanted colsum_pre; the final norm's pooled backward): (768,) fp32 each, per device, accumulated into and never
+    read.  Owned here, never a parameter's .grad."""
+    t = _LN_THROWAWAY.get(str(device))
+    if t is None:
+        t = _LN_THROWAWAY[str(device)] = torch.zeros((2, 768), dtype=torch.float32, device=device)
+    return t[0], t[1]
+
+
+def layernorm_bwd(dy, x, gamma, eps, dx, dgamma=None, dbeta=None, rows=None, dy2=None, accumulate=True, map_mode=MAP_IDENTITY, map_p0=0, map_p1=0,
                   drop_p=0.0, drop_seed=0, emit=None):
     """dx[map(m)] (+)= dLN; dgamma/dbeta (fp32, pre-initialised) are accumulated.  x, dx: fp32 (..., 768).
+    dgamma = dbeta = None: gamma and beta are frozen -- the data-only kernel (the same dx and emitted rows bit for bit, no column sums, no
+    reduce launch).  One of the two None: the trainable one is accumulated, the other goes to a throw-away buffer.  A wanted colsum_pre with
+    the None pair runs the column-sum kernel into the throw-away pair (ln_throwaway_pair).
     emit: None, or a dict(mode=EMIT_*, rows=<output rows>, dtype=<operand dtype, default dy's>, T=, N=, scale=<fp32 row scales>, group=, drop_p=, drop_seed=, colsum_pre=,
     extra_cls=) -- the finished gradient rows ALSO leave as the dy-dtype operand rows of the next GEMMs (alpro_layernorm_bwd_emit, what a
     following gather_cast would build); then returns (dx, emitted (rows, 768) tensor)."""
     lib = load()
-    _dev(dy); _dev(x, torch.float32); _dev(dx, torch.float32); _dev(dgamma, torch.float32); _dev(dbeta, torch.float32)
+    _dev(dy); _dev(x, torch.float32); _dev(dx, torch.float32)
+    if (dgamma is None) != (dbeta is None) or (dgamma is None and emit is not None and emit.get("colsum_pre") is not None):
+        tg, tb = ln_throwaway_pair(dy.device)
+        dgamma, dbeta = (tg if dgamma is None else dgamma), (tb if dbeta is None else dbeta)
+    if dgamma is not None:
+        _dev(dgamma, torch.float32); _dev(dbeta, torch.float32)
     D = x.shape[-1]
     rows = rows if rows is not None else dy.numel() // D
     common = (_ptr(dy), _CODE[dy.dtype], D, _ptr(_dev(dy2, torch.float32)) if dy2 is not None else None, _ptr(x), D,
@@ -979,6 +1001,18 @@ def gemm_tn_acc(a, b, c, colsum=None, atomic=None):
     _check(lib.alpro_gemm_tn_acc_ws(_ptr(a), a.stride(0), _ptr(b), b.stride(0), _ptr(c), c.stride(0), _CODE[a.dtype], M, N, K, _ptr(colsum),
                                     _ptr(ws), ws.numel(), _stream()), "alpro_gemm_tn_acc_ws")
     return c
+
+
+def colsum_tn(a, K, colsum):
+    """colsum (N,) fp32 += a.sum(0) with the bits gemm_tn_acc(a, b (M, K), c, colsum) gives its bias gradient (alpro_colsum_tn), without the
+    weight-gradient GEMM: the bias gradient of a Linear whose weight is frozen.  16-bit a (M, N), rows contiguous."""
+    lib = load()
+    _dev(a); _dev(colsum, torch.float32)
+    M, N = a.shape
+    assert colsum.numel() >= N
+    ws = _tn_workspace(a.device, lib.alpro_gemm_tn_workspace_bytes(M, N, K))
+    _check(lib.alpro_colsum_tn(_ptr(a), a.stride(0), _CODE[a.dtype], M, N, K, _ptr(colsum), _ptr(ws), ws.numel(), _stream()), "alpro_colsum_tn")
+    return colsum
 
 
 def transpose_jobs(pairs):

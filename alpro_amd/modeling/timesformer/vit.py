@@ -150,6 +150,31 @@ def _aux_stream(device):
     return s
 
 
+def _draws_per_call(blk):
+    """True if a forward of the block draws from a random stream PER CALL (train mode only): its two attention-dropout seeds, or drop-path masks that
+    sample_drop_paths did not draw for the whole step beforehand."""
+    if not blk.training:
+        return False
+    live_dp = isinstance(blk.drop_path, DropPath) and bool(blk.drop_path.drop_prob)
+    return blk.attn.attn_drop.p > 0 or blk.temporal_attn.attn_drop.p > 0 or (live_dp and not getattr(blk, "_presampled", None))
+
+
+def run_prefix_blocks(blocks, tok, B, T, W):
+    """The frozen prefix of a training forward (tr.frozen_prefix): the no-grad forward of `blocks`, in place -- nothing is saved for a backward
+    and no W^T operand is built -- through run_blocks with what it brings (fused temporal launch, two half batches on two streams, deferred
+    temporal add).  Train-mode stochasticity is the reference's: the drop-path masks are the ones sample_drop_paths drew for the whole step
+    (run_blocks hands each half batch its rows of them), and a block with attention dropout draws its two seeds ONCE, so the seed stream reaches
+    the trainable blocks where the all-trainable step's does -- two half-batch calls would draw twice, so blocks that draw per call take the
+    whole batch on the launch stream."""
+    with torch.no_grad():
+        if any(_draws_per_call(blk) for blk in blocks):
+            for blk in blocks:
+                tok = blk(tok, B, T, W)
+            _ClsSide.join(tok.device)
+            return tok
+        return run_blocks(blocks, tok, B, T, W)
+
+
 def run_blocks(blocks, tok, B, T, W):
     """The no-grad forward through `blocks` (tok updated in place and returned), CLS chains joined.
 
@@ -175,14 +200,24 @@ def run_blocks(blocks, tok, B, T, W):
     ev = main.record_event()        # the embedding is written
     for i, blk in enumerate(blocks):
         r0 = weights.operand_rebuilds()
-        blk(lo, h, T, W)
+        # drop-path masks drawn for the whole batch beforehand (sample_drop_paths; the frozen prefix of a training step): the rows of every mask are
+        # clip-major and B is even here (split_streams refuses an odd B), so each half batch is handed its half of the three masks explicitly --
+        # nothing is left on the module
+        pre = getattr(blk, "_presampled", None)
+        kw_lo = kw_hi = {}
+        if pre:
+            N = (tok.shape[1] - 1) // T
+            masks = [pre[n] for n in (B * N, B * T, B)]    # temporal, spatial, MLP rows (distinct counts: sample_drop_paths draws only then)
+            blk._presampled = None
+            kw_lo, kw_hi = dict(drop_masks=tuple(m[:m.numel() // 2] for m in masks)), dict(drop_masks=tuple(m[m.numel() // 2:] for m in masks))
+        blk(lo, h, T, W, **kw_lo)
         if weights.operand_rebuilds() != r0:   # the launch stream (re)built operand copies of this block: the second stream may only read them afterwards
             ev = main.record_event()
         with torch.cuda.stream(aux):
             if ev is not None:
                 aux.wait_event(ev)
                 ev = None
-            blk(hi, h, T, W)
+            blk(hi, h, T, W, **kw_hi)
             if lockstep or i == len(blocks) - 1:
                 _ClsSide.join(dev)
                 ev_hi = aux.record_event()
@@ -327,9 +362,11 @@ class Block(nn.Module):
         seed_s = rt.next_dropout_seed() if ps > 0 else 0
         return (pt if seed_t else 0.0), seed_t, (ps if seed_s else 0.0), seed_s
 
-    def forward(self, x, B, T, W):
-        """x: (B, 1 + N*T, D) fp32 contiguous token tensor; updated IN PLACE and returned (inference path)."""
-        return self._forward(x, B, T)
+    def forward(self, x, B, T, W, drop_masks=None):
+        """x: (B, 1 + N*T, D) fp32 contiguous token tensor; updated IN PLACE and returned (inference path).
+        drop_masks: (temporal (B*N,), spatial (B*T,), MLP (B,)) drop-path row scales to apply instead of drawing them (run_blocks: a half batch's
+        rows of the masks drawn for the whole step)."""
+        return self._forward(x, B, T, drop_masks=drop_masks)
 
     def forward_train(self, x, B, T, W):
         """Same arithmetic as forward() but out of place: fresh buffers (the backward needs every LayerNorm input); returns (out, saved) for the
@@ -343,7 +380,7 @@ class Block(nn.Module):
         (vit.py:165-212); eval mode only (no drop-path).  Returns the block output's CLS rows, (B, D) fp32."""
         return self._forward(x, B, T, cls_only=True)
 
-    def _forward(self, x, B, T, save=False, cls_only=False):
+    def _forward(self, x, B, T, save=False, cls_only=False, drop_masks=None):
         """The divided space-time block (vit.py:146-212), every stage stated once.  The residual stream goes
             x --temporal branch--> xt --spatial branch--> x2 --MLP--> out
         and the three entry points differ in where those four live and in what is kept:
@@ -362,7 +399,7 @@ class Block(nn.Module):
             rs_t = rs_s = rs_m = {}
             seeds = ap_t, seed_t, ap_s, seed_s = 0.0, 0, 0.0, 0
         else:
-            drop_t, drop_s, drop_m = self._drop(B * N, dev), self._drop(B * T, dev), self._drop(B, dev)
+            drop_t, drop_s, drop_m = drop_masks if drop_masks is not None else (self._drop(B * N, dev), self._drop(B * T, dev), self._drop(B, dev))
             rs_t, rs_s, rs_m = (dict(row_scale=d, row_scale_group=g) for d, g in ((drop_t, T), (drop_s, N + 1), (drop_m, S)))
             seeds = ap_t, seed_t, ap_s, seed_s = self._attn_drop_seeds()   # the backward regenerates the masks from these
         # precise CLS rows, decided once: off (cp False) | on the launch stream (cp, side None) | on the side stream (side)
@@ -487,36 +524,54 @@ class Block(nn.Module):
         if G is None:
             G = hip.gather_cast(dx, dt, rows=B * N * T, map_mode=hip.MAP_SKIP_CLS, map_p0=N * T, row_scale=sv["drop_t"], row_scale_group=T,
                                 colsum_pre=tr.bias_grad(fc.bias))
+        # frozen members (requires_grad, read now): dWe feeds dWfc and dWp, db1 feeds dWfc and dbp; with none of the three trainable neither is
+        # formed (temporal_fc.bias took its column sums from whoever built G)
+        t_fc, t_p, t_bp = tr.trainable(fc.weight), tr.trainable(ta.proj.weight), tr.trainable(ta.proj.bias)
+        if not (t_fc or t_p or t_bp):
+            return tr.dgrad(G, mg["wT"])
         ws = sv.get("ws")  # zeroed slice of the per-backward workspace (one fill for all 12 blocks), else allocate
         if ws is None:
             ws = torch.zeros(D * D + D, dtype=torch.float32, device=dev)
         dWe, db1 = ws[:D * D].view(D, D), ws[D * D:]
-        if dt != torch.float32:
-            hip.gemm_tn_acc(G, sv["a_t"], dWe, colsum=db1)                       # dWe = G^T a, db1 = colsum(G)
+        cs = db1 if (t_fc or t_bp) else None
+        if dt != torch.float32 and not (t_fc or t_p):
+            hip.colsum_tn(G, sv["a_t"].shape[1], db1)                            # only dbp wanted: db1 = colsum(G) with the GEMM's bits, no dWe
+        elif dt != torch.float32:
+            hip.gemm_tn_acc(G, sv["a_t"], dWe, colsum=cs)                        # dWe = G^T a, db1 = colsum(G)
+        elif t_fc or t_p:
+            hip.gemm(hip.transpose(G, colsum=cs), hip.transpose(sv["a_t"]), out=dWe, out_dtype=torch.float32)
         else:
-            hip.gemm(hip.transpose(G, colsum=db1), hip.transpose(sv["a_t"]), out=dWe, out_dtype=torch.float32)
+            db1.add_(G.sum(0, dtype=torch.float32))
         da = tr.dgrad(G, mg["wT"])                                              # d(a) = G We
         if sv.get("defer_product_rule"):   # the bank applies the product rule for a whole group of blocks at once (_MergedTProjBank.product_rule)
             return da
         # product rule back onto the two real parameters (768^3 each).  Exact mode: fp32 MFMA.  16-bit modes: 16-bit operands with fp32
         # accumulation into the fp32 gradient, like every other weight gradient on this path (dWe itself came from 16-bit operands) --
         # the two fp32 768^3 GEMMs were 57 us each on 36 workgroups, 2 x 12 of them per step.
-        g_fc, g_p = tr.grad_buffer(fc.weight, zero=True)[0], tr.grad_buffer(ta.proj.weight, zero=True)[0]
+        g_fc, g_p = tr.grad_target(fc.weight), tr.grad_target(ta.proj.weight)     # None: frozen, its term of the product rule is not evaluated
         if dt != torch.float32:
-            hip.gemm(hip.cast(dWe, dt), self._w("t_proj", ta.proj, dt), out=g_fc, out_dtype=torch.float32, residual=g_fc)   # += dWe Wp^T
-            hip.gemm(self._wt("t_fc", fc, dt)[:, :D], hip.transpose(dWe, out_dtype=dt), out=g_p, out_dtype=torch.float32, residual=g_p)  # += Wfc^T dWe
+            if g_fc is not None:
+                hip.gemm(hip.cast(dWe, dt), self._w("t_proj", ta.proj, dt), out=g_fc, out_dtype=torch.float32, residual=g_fc)   # += dWe Wp^T
+            if g_p is not None:
+                hip.gemm(self._wt("t_fc", fc, dt)[:, :D], hip.transpose(dWe, out_dtype=dt), out=g_p, out_dtype=torch.float32, residual=g_p)  # += Wfc^T dWe
         else:
-            hip.gemm(dWe, wp.contiguous(), out=g_fc, out_dtype=torch.float32, residual=g_fc)                     # += dWe Wp^T
-            hip.gemm(hip.transpose(wf.contiguous()), hip.transpose(dWe), out=g_p, out_dtype=torch.float32, residual=g_p)  # += Wfc^T dWe
-        g_fc.addr_(db1, bp)                                                                                       # += db1 bp^T
-        tr.bias_grad(ta.proj.bias).add_(torch.mv(wf.t(), db1))                                                    # += Wfc^T db1
+            if g_fc is not None:
+                hip.gemm(dWe, wp.contiguous(), out=g_fc, out_dtype=torch.float32, residual=g_fc)                     # += dWe Wp^T
+            if g_p is not None:
+                hip.gemm(hip.transpose(wf.contiguous()), hip.transpose(dWe), out=g_p, out_dtype=torch.float32, residual=g_p)  # += Wfc^T dWe
+        if g_fc is not None:
+            g_fc.addr_(db1, bp)                                                                                   # += db1 bp^T
+        if t_bp:
+            tr.bias_grad(ta.proj.bias).add_(torch.mv(wf.t(), db1))                                                # += Wfc^T db1
         return da
 
     def backward(self, sv, dx, dz=None, emit_for=None):
         """dx: gradient w.r.t. the block output, (B, S, D) fp32; overwritten with the gradient w.r.t. the block input.
         dz: the operand rows drop_m * dx in the compute dtype if whoever produced dx already emitted them (the final norm's backward, or
         the next block's temporal-LayerNorm backward), else None -> built here by alpro_gather_cast.
-        emit_for: saved state of the PREVIOUS block (the next one to run its backward): its dz is emitted by this block's last kernel.
+        emit_for: saved state of the PREVIOUS block (the next one to run its backward): its dz is emitted by this block's last kernel; None
+        for the first block of the anchored run (block 0, or the first block behind a frozen prefix).
+        Frozen parameters get no gradient and no work: see tr.wgrad / tr.grad_target.
         Returns (dx, dz for the previous block or None)."""
         B, T, N, S, D, H = sv["dims"]
         dt = sv["dt"]
@@ -530,7 +585,7 @@ class Block(nn.Module):
         del dz
         tr.wgrad(du, sv["h2"], self.mlp.fc1.weight, self.mlp.fc1.bias)
         dh2 = tr.dgrad(du, self._wt("fc1", self.mlp.fc1, dt))
-        g, b_ = tr.grad_buffer(self.norm2.weight, zero=True)[0], tr.grad_buffer(self.norm2.bias, zero=True)[0]
+        g, b_ = tr.grad_target(self.norm2.weight), tr.grad_target(self.norm2.bias)   # (None: frozen -- both None is the data-only LayerNorm backward)
         # ---- spatial: x2 = scatter(xt + drop_s * proj(attn(qkv(LN1(gather(xt)))))), CLS averaged over frames
         # norm2's backward hands the finished d(x2) rows straight to the spatial projection's GEMMs (frame-token order, drop_s, CLS / T)
         _, dpo = hip.layernorm_bwd(dh2, sv["x2"], self.norm2.weight, VIT_EPS, dx, g, b_,
@@ -541,7 +596,7 @@ class Block(nn.Module):
         dqkv = hip.attn_bwd(sv["qkv_s"], sv["a_s"], da, sv["lse_s"], B * T, N + 1, H, sa.scale, drop_p=ap_s, drop_seed=seed_s)
         tr.wgrad(dqkv, sv["hs"], sa.qkv.weight, sa.qkv.bias)
         dhs = tr.dgrad(dqkv, self._wt("s_qkv", sa.qkv, dt))
-        g, b_ = tr.grad_buffer(self.norm1.weight, zero=True)[0], tr.grad_buffer(self.norm1.bias, zero=True)[0]
+        g, b_ = tr.grad_target(self.norm1.weight), tr.grad_target(self.norm1.bias)
         # ---- temporal: xt[:, 1:] = x[:, 1:] + fc(drop_t * proj(attn(qkv(LN_t(x[:, 1:])))))
         G = None
         if sv["merged"]:  # norm1's backward emits drop_t * d(xt)[:, 1:] and the temporal_fc bias gradient (unscaled column sums)
@@ -562,7 +617,7 @@ class Block(nn.Module):
         dqkv = hip.attn_temporal_bwd(sv["qkv_t"], sv["a_t"], da, sv["lse_t"], T, H, ta.scale, drop_p=ap_t, drop_seed=seed_t)
         tr.wgrad(dqkv, sv["h"], ta.qkv.weight, ta.qkv.bias)
         dh = tr.dgrad(dqkv, self._wt("t_qkv", ta.qkv, dt))
-        g, b_ = tr.grad_buffer(self.temporal_norm1.weight, zero=True)[0], tr.grad_buffer(self.temporal_norm1.bias, zero=True)[0]
+        g, b_ = tr.grad_target(self.temporal_norm1.weight), tr.grad_target(self.temporal_norm1.bias)
         dz_prev = None
         if emit_for is not None:  # ... and the temporal norm's backward emits the previous block's MLP operand (its drop_m, all rows incl. CLS)
             _, dz_prev = hip.layernorm_bwd(dh, sv["x"], self.temporal_norm1.weight, VIT_EPS, dx, g, b_, rows=B * N * T, map_mode=hip.MAP_SKIP_CLS,
@@ -686,14 +741,24 @@ class _MergedTProjBank:
         b["ws"].zero_()
         return b["ws"]
 
-    def product_rule(self, lo, hi, dt):
-        """Blocks lo..hi-1: dW_fc += dW_e W_p^T + db1 b_p^T, dW_p += W_fc^T dW_e, db_p += W_fc^T db1 -- 16-bit operands with fp32 accumulation
-        into the fp32 gradients, like every other weight gradient on this path.  Five launches for the whole group."""
+    def all_trainable(self, idx):
+        """True if the three parameters the batched product rule writes gradients for are all trainable in block idx; a block with a frozen
+        member applies the rule itself, member by member (Block._merged_tproj_backward)."""
+        blk = self.blocks[idx]
+        return all(tr.trainable(p) for p in (blk.temporal_fc.weight, blk.temporal_attn.proj.weight, blk.temporal_attn.proj.bias))
+
+    def product_rule(self, lo, hi, dt, idx=None):
+        """Blocks lo..hi-1 -- or, with idx, those of them listed there (ascending, each all_trainable): dW_fc += dW_e W_p^T + db1 b_p^T,
+        dW_p += W_fc^T dW_e, db_p += W_fc^T db1 -- 16-bit operands with fp32 accumulation into the fp32 gradients, like every other weight gradient
+        on this path.  Five launches for the whole group."""
         assert dt != torch.float32 and self.bwd is not None
-        b, blocks = self.bwd, self.blocks[lo:hi]
+        idx = tuple(range(lo, hi)) if idx is None else tuple(idx)
+        if not idx:
+            return
+        b, blocks = self.bwd, [self.blocks[i] for i in idx]
         D = blocks[0].temporal_fc.weight.shape[0]
         ops = []
-        for i, blk in zip(range(lo, hi), blocks):
+        for i, blk in zip(idx, blocks):
             ta, fc = blk.temporal_attn, blk.temporal_fc
             g_fc, g_p = tr.grad_buffer(fc.weight, zero=True)[0], tr.grad_buffer(ta.proj.weight, zero=True)[0]
             g_bp = tr.bias_grad(ta.proj.bias)
@@ -701,7 +766,7 @@ class _MergedTProjBank:
                             wf=fc.weight.detach(), bp=ta.proj.bias.detach()))
         sig = tuple((o["wp_dt"].data_ptr(), o["wfT_dt"].data_ptr(), o["g_fc"].data_ptr(), o["g_p"].data_ptr(), o["g_bp"].data_ptr(), o["wf"].data_ptr())
                     for o in ops)
-        tb = self._bwd_tables.get((lo, hi))
+        tb = self._bwd_tables.get(idx)
         if tb is None or tb["sig"] != sig:
             ga, gbb = hip.GemmBatch(), hip.GemmBatch()
             for o in ops:
@@ -712,7 +777,8 @@ class _MergedTProjBank:
                       t_dwe=hip.transpose_jobs([(b["ws"][o["i"], :D * D].view(D, D), b["dweT"][o["i"]]) for o in ops]),
                       t_small=hip.tproj_jobs([dict(wfc=o["wf"], bp=o["bp"], db1=b["ws"][o["i"], D * D:], g_fc=o["g_fc"], g_bp=o["g_bp"]) for o in ops],
                                              b["ws"].device))
-            self._bwd_tables[(lo, hi)] = tb
+            self._bwd_tables[idx] = tb
+        lo, hi = idx[0], idx[-1] + 1
         hip.cast(b["ws"][lo:hi].reshape(-1), dt, out=b["ws_dt"][lo:hi].reshape(-1))
         hip.transpose_batch(*tb["t_dwe"], dt)
         tb["ga"].launch()
@@ -832,27 +898,39 @@ class VisionTransformer(nn.Module):
         """Gradients of patch_embed.proj / cls_token / pos_embed / time_embed from dtok (B, 1+N*T, D)."""
         dt = rows.dtype
         D = self.embed_dim
-        drows = hip.gather_cast(dtok, dt, rows=B * T * N, map_mode=hip.MAP_PATCH_EMBED, map_p0=T, map_p1=N)
         pe = self.patch_embed.proj
-        if dt != torch.float32:  # 16-bit operands: in-place TN weight gradient (contraction over the B*T*N patch rows)
-            gw = tr.grad_buffer(pe.weight, zero=True)[0]
-            hip.gemm_tn_acc(drows, rows, gw.view(D, -1))
-        else:
-            gw, existed = tr.grad_buffer(pe.weight)
-            gw2 = gw.view(D, -1)
-            hip.gemm(hip.transpose(drows), hip.transpose(rows), out=gw2, out_dtype=torch.float32, residual=gw2 if existed else None)
-        dtable = dtok[:, 1:].sum(0).view(N, T, D)  # small (N*T, D) reductions: parameter-sized, stay in torch
-        tr.add_grad(pe.bias, dtable.sum((0, 1)))
-        dcls = dtok[:, 0].sum(0)
+        if tr.trainable(pe.weight):   # (frozen: neither the operand rows nor the GEMM)
+            drows = hip.gather_cast(dtok, dt, rows=B * T * N, map_mode=hip.MAP_PATCH_EMBED, map_p0=T, map_p1=N)
+            if dt != torch.float32:  # 16-bit operands: in-place TN weight gradient (contraction over the B*T*N patch rows)
+                gw = tr.grad_buffer(pe.weight, zero=True)[0]
+                hip.gemm_tn_acc(drows, rows, gw.view(D, -1))
+            else:
+                gw, existed = tr.grad_buffer(pe.weight)
+                gw2 = gw.view(D, -1)
+                hip.gemm(hip.transpose(drows), hip.transpose(rows), out=gw2, out_dtype=torch.float32, residual=gw2 if existed else None)
+        # small (N*T, D) reductions: parameter-sized, stay in torch; each one is formed only for a trainable table
+        t_pos, t_time, t_cls, t_b = (tr.trainable(q) for q in (self.pos_embed, self.time_embed, self.cls_token, pe.bias))
+        dtable = dtok[:, 1:].sum(0).view(N, T, D) if (t_pos or t_time or t_b) else None
+        if t_b:
+            tr.add_grad(pe.bias, dtable.sum((0, 1)))
+        dcls = dtok[:, 0].sum(0) if (t_cls or t_pos) else None
         tr.add_grad(self.cls_token, dcls)
         pidx, tidx = self._embed_index(N, T, Wg) if Wg is not None else (None, None)
-        dpos, dtime = dtable.sum(1), dtable.sum(0)
-        if pidx is not None:  # resampled tables: scatter the gradients back onto the slots they were read from
-            dpos = torch.zeros((self.pos_embed.size(1) - 1, D), dtype=dpos.dtype, device=dpos.device).index_put_((pidx,), dpos, accumulate=True)   # (sorted accumulate: fixed order, unlike index_add_'s atomics)
-        if tidx is not None:
-            dtime = torch.zeros((self.time_embed.size(1), D), dtype=dtime.dtype, device=dtime.device).index_put_((tidx,), dtime, accumulate=True)
-        tr.add_grad(self.pos_embed, torch.cat([dcls[None], dpos], 0))
-        tr.add_grad(self.time_embed, dtime)
+        if t_pos:
+            dpos = dtable.sum(1)
+            if pidx is not None:  # resampled tables: scatter the gradients back onto the slots they were read from
+                dpos = torch.zeros((self.pos_embed.size(1) - 1, D), dtype=dpos.dtype, device=dpos.device).index_put_((pidx,), dpos, accumulate=True)   # (sorted accumulate: fixed order, unlike index_add_'s atomics)
+            tr.add_grad(self.pos_embed, torch.cat([dcls[None], dpos], 0))
+        if t_time:
+            dtime = dtable.sum(0)
+            if tidx is not None:
+                dtime = torch.zeros((self.time_embed.size(1), D), dtype=dtime.dtype, device=dtime.device).index_put_((tidx,), dtime, accumulate=True)
+            tr.add_grad(self.time_embed, dtime)
+
+    def stage_params(self):
+        """Parameter lists of the encoder's stages in forward order -- embedding, block 0, block 1, ... -- for tr.frozen_prefix."""
+        emb = list(self.patch_embed.parameters()) + [self.cls_token, self.pos_embed, self.time_embed]
+        return [emb] + [list(blk.parameters()) for blk in self.blocks]
 
     def forward_features(self, x, return_all_tokens=False):
         B = x.shape[0]
@@ -928,12 +1006,21 @@ class TimeSformer(nn.Module):
             return tr.run_anchored(_VisualRun(self, mode), [x], list(self.parameters()))
         m = self.model
         B = x.shape[0]
-        tok, T, W, N = m._embed(x)
-        tok = run_blocks(m.blocks, tok, B, T, W)
-        if mode == hip.POOL_TEMPORAL:
-            out32, _ = hip.vit_final_pool(tok, m.norm.weight, m.norm.bias, VIT_EPS, B, T, N, torch.float32)
-        else:
-            out32, _ = hip.vit_final_pool_mode(tok, m.norm.weight, m.norm.bias, VIT_EPS, B, T, N, torch.float32, mode)
+        in_step = torch.is_grad_enabled()   # a wholly frozen encoder inside a training step: the frozen prefix is the whole encoder
+        with torch.no_grad():               # (run_blocks forks its two half-batch streams only without grad)
+            tok, T, W, N = m._embed(x)
+            if in_step:   # as _VisualRun.forward treats a prefix: the step's drop-path masks in one draw, one pair of dropout seeds per block
+                if B * N != B * T and B * T != B:
+                    sample_drop_paths(m.blocks, B, T, N, tok.device)
+                tok = run_prefix_blocks(m.blocks, tok, B, T, W)
+                for blk in m.blocks:
+                    blk._presampled = None
+            else:
+                tok = run_blocks(m.blocks, tok, B, T, W)
+            if mode == hip.POOL_TEMPORAL:
+                out32, _ = hip.vit_final_pool(tok, m.norm.weight, m.norm.bias, VIT_EPS, B, T, N, torch.float32)
+            else:
+                out32, _ = hip.vit_final_pool_mode(tok, m.norm.weight, m.norm.bias, VIT_EPS, B, T, N, torch.float32, mode)
         return out32
 
     def forward_cls(self, x):
@@ -969,12 +1056,22 @@ class _VisualRun:
     def forward(self, x):
         m = self.enc.model
         B = x.shape[0]
+        # the frozen prefix (requires_grad is read NOW, at every forward): k leading stages -- embedding, block 0, ... -- hold no trainable parameter
+        # and pixels need no gradient here, so those blocks run their no-grad forward and the backward ends at the input of block k - 1
+        k = tr.frozen_prefix(m.stage_params(), torch.is_tensor(x) and x.requires_grad)
+        self.nfro, self.embed_frozen = max(k - 1, 0), k >= 1
         tok, T, W, N = m._embed(x)
-        self.rows, self.dims, self.Wg = m._last_rows, (B, T, N), W
+        self.rows, self.dims, self.Wg = (None if self.embed_frozen else m._last_rows), (B, T, N), W
+        if self.embed_frozen:
+            m._last_rows = None   # (the patch rows are the weight gradient's operand: nobody reads them)
         self.saved = []
         if B * N != B * T and B * T != B:  # (the table is keyed by row count: the three counts must differ, else draw per call)
             sample_drop_paths(m.blocks, B, T, N, tok.device)
-        for blk in m.blocks:
+        if self.nfro:
+            tok = run_prefix_blocks(m.blocks[:self.nfro], tok, B, T, W)
+            for blk in m.blocks[:self.nfro]:
+                blk._presampled = None
+        for blk in m.blocks[self.nfro:]:
             tok, sv = blk.forward_train(tok, B, T, W)
             blk._presampled = None
             self.saved.append(sv)
@@ -990,24 +1087,35 @@ class _VisualRun:
         m = self.enc.model
         B, T, N = self.dims
         D = m.embed_dim
-        g, b_ = tr.grad_buffer(m.norm.weight, zero=True)[0], tr.grad_buffer(m.norm.bias, zero=True)[0]
+        nb, nfro = len(m.blocks), self.nfro
+        g, b_ = tr.grad_target(m.norm.weight), tr.grad_target(m.norm.bias)
         S_ = 1 + N * T   # the final norm's backward emits the last block's MLP operand rows (its drop-path scale)
+        last = self.saved[-1] if self.saved else None   # None: every block is in the frozen prefix, only the final norm is trainable
+        emit_dt = last["dt"] if last is not None else rt.compute_dtype()
         if self.mode == hip.POOL_TEMPORAL:
             # final norm + temporal mean pool (vit.py:372,484-492): every frame token receives dout / T, the CLS token dout
             dy = torch.empty((B, 1 + N * T, D), dtype=torch.float32, device=dout.device)
             dy[:, 0] = dout[:, 0]
             torch.mul(dout[:, 1:].unsqueeze(2).expand(B, N, T, D), 1.0 / T, out=dy[:, 1:].view(B, N, T, D))  # one broadcast pass (was mul + repeat_interleave + copy)
             dtok = torch.empty_like(dy)
-            _, dz = hip.layernorm_bwd(dy.view(-1, D), self.tok, m.norm.weight, VIT_EPS, dtok, g, b_, accumulate=False,
-                                      emit=dict(mode=hip.EMIT_ROWS, rows=B * S_, dtype=self.saved[-1]["dt"], scale=self.saved[-1]["drop_m"], group=S_))
-            del dy
+            r = hip.layernorm_bwd(dy.view(-1, D), self.tok, m.norm.weight, VIT_EPS, dtok, g, b_, accumulate=False,
+                                  emit=dict(mode=hip.EMIT_ROWS, rows=B * S_, dtype=emit_dt, scale=last["drop_m"], group=S_) if last is not None else None)
+            dz = r[1] if last is not None else None
+            del dy, r
         else:   # spatial / none (vit.py:493-499): dout is un-pooled inside the LayerNorm-backward pass itself, dy is never built
-            dtok, dz = hip.vit_final_pool_mode_bwd(dout, self.tok, m.norm.weight, VIT_EPS, g, b_, B, T, N, self.mode,
-                                                   emit=dict(dtype=self.saved[-1]["dt"], scale=self.saved[-1]["drop_m"], group=S_))
+            if g is None or b_ is None:   # frozen: this kernel (once per step) keeps its column sums and adds them to a pair nobody reads
+                tg, tb = hip.ln_throwaway_pair(dout.device)
+                g, b_ = (tg if g is None else g), (tb if b_ is None else b_)
+            r = hip.vit_final_pool_mode_bwd(dout, self.tok, m.norm.weight, VIT_EPS, g, b_, B, T, N, self.mode,
+                                            emit=dict(dtype=emit_dt, scale=last["drop_m"], group=S_) if last is not None else None)
+            dtok, dz = r if last is not None else (r, None)
+        if last is None:
+            self.saved = self.rows = self.tok = None
+            return None
         bank = m.blocks[0]._bank()
-        dt_run = self.saved[-1]["dt"]
+        dt_run = last["dt"]
         banked = bank is not None and dt_run != torch.float32 and all(sv["merged"] for sv in self.saved)
-        ws = bank.workspace(dt_run, dout.device) if banked else torch.zeros((len(m.blocks), D * D + D), dtype=torch.float32, device=dout.device)
+        ws = bank.workspace(dt_run, dout.device) if banked else torch.zeros((nb, D * D + D), dtype=torch.float32, device=dout.device)
         # Data parallel: in the pretraining / retrieval models this node is the LAST one autograd runs (created first, its input needs
         # no gradient), so every gradient outside the visual encoder is final now and can be exchanged while the ViT backward (half of
         # the backward pass) runs; the blocks' own gradients follow four blocks at a time (alpro_amd.dist.grads_final -> FlatAdamW).
@@ -1017,20 +1125,23 @@ class _VisualRun:
         overlap = dist.collectives_active() and not getattr(self, "others_pending", False)
         if overlap:
             dist.grads_final(all_but=list(self.enc.parameters()))
-        nb = len(m.blocks)
-        group_hi = nb
-        for i, (blk, sv) in enumerate(zip(reversed(m.blocks), reversed(self.saved))):
-            sv["ws"] = ws[nb - 1 - i]
-            sv["defer_product_rule"] = banked
-            dtok, dz = blk.backward(sv, dtok, dz=dz, emit_for=self.saved[nb - 2 - i] if i + 1 < nb else None)
-            if (i + 1) % 4 == 0 or i + 1 == nb:   # a group of blocks is through: their merged-projection product rule in batched launches ...
-                lo = nb - 1 - i
+        group_hi, group_rule = nb, []
+        for j in range(nb - 1, nfro - 1, -1):   # block j; blocks below nfro are the frozen prefix: the backward ends at block nfro's input
+            blk, sv = m.blocks[j], self.saved[j - nfro]
+            sv["ws"] = ws[j]
+            sv["defer_product_rule"] = banked and bank.all_trainable(j)   # (a block with a frozen member applies the rule itself)
+            if sv["defer_product_rule"]:
+                group_rule.insert(0, j)
+            dtok, dz = blk.backward(sv, dtok, dz=dz, emit_for=self.saved[j - 1 - nfro] if j > nfro else None)
+            done = nb - j
+            if done % 4 == 0 or j == nfro:   # a group of blocks is through: their merged-projection product rule in batched launches ...
                 if banked:
-                    bank.product_rule(lo, group_hi, dt_run)
-                if overlap and i + 1 < nb:       # ... and then their gradients are final (the last group goes at synchronize())
-                    dist.grads_final(params=[p for b in m.blocks[lo:group_hi] for p in b.parameters()] + (list(m.norm.parameters()) if group_hi == nb else []))
-                group_hi = lo
+                    bank.product_rule(j, group_hi, dt_run, idx=group_rule)
+                if overlap and j > nfro:       # ... and then their gradients are final (the last group goes at synchronize())
+                    dist.grads_final(params=[p for b in m.blocks[j:group_hi] for p in b.parameters()] + (list(m.norm.parameters()) if group_hi == nb else []))
+                group_hi, group_rule = j, []
             sv.clear()
-        m._embed_backward(self.rows, dtok, B, T, N, self.Wg)
+        if not self.embed_frozen:
+            m._embed_backward(self.rows, dtok, B, T, N, self.Wg)
         self.saved = self.rows = self.tok = None
         return None  # pixels need no gradient

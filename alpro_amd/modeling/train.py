@@ -16,8 +16,37 @@ from alpro_amd import hip
 from alpro_amd.modeling.weights import param_version
 
 
+def trainable(p):
+    """True if `p` is a parameter that receives a gradient: the ONE place the hand-written backward reads `requires_grad` (at every call:
+    nothing derived from the flag is kept across steps, so a parameter may be frozen for an epoch and unfrozen later)."""
+    return p is not None and p.requires_grad
+
+
+def grad_target(p, zero=True):
+    """The fp32 .grad buffer of a trainable parameter (allocated on first use), or None for a frozen one -- the form every kernel wrapper
+    takes for "no gradient wanted" (colsum=None, dgamma=None, ...).  A frozen parameter's .grad is never touched: it stays None, or whatever
+    an earlier trainable step left there."""
+    return grad_buffer(p, zero=zero)[0] if trainable(p) else None
+
+
+def frozen_prefix(stages, input_needs_grad=False):
+    """Length of the frozen prefix of an encoder: the longest run of leading stages none of whose parameters is trainable -- 0 when the
+    encoder's input itself needs a gradient (the backward then has to reach it through every stage).
+    stages: one list of parameters per stage, in forward order (ViT: embedding, block 0, block 1, ...; BERT: embeddings, layer 0, ...).
+    A prefix stage runs its no-grad forward (nothing saved, no W^T operands) and the anchored run starts behind it; a frozen stage BEHIND a
+    trainable one is not part of the prefix (the data gradient passes through it).  Pure: reads requires_grad, touches no device."""
+    if input_needs_grad:
+        return 0
+    n = 0
+    for params in stages:
+        if any(trainable(p) for p in params):
+            break
+        n += 1
+    return n
+
+
 def grad_buffer(p, zero=False):
-    """Return (p.grad, existed).  Allocates an fp32 buffer on first use."""
+    """Return (p.grad, existed).  Allocates an fp32 buffer on first use.  Callers ask for trainable parameters only (grad_target)."""
     if p.grad is not None and (p.grad.numel() <= 1 or any(p.grad.stride())):   # (a stride-0 placeholder of optim.zero_none_grad is "no buffer yet")
         return p.grad, True
     p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format) if zero else torch.empty_like(p, memory_format=torch.contiguous_format)
@@ -25,6 +54,9 @@ def grad_buffer(p, zero=False):
 
 
 def add_grad(p, g):
+    """p.grad += g (a parameter-sized tensor); nothing for a frozen p, whose .grad stays as it is."""
+    if not trainable(p):
+        return
     if p.grad is None or (p.grad.numel() > 1 and not any(p.grad.stride())):
         p.grad = g.detach().clone().reshape(p.shape).contiguous()
     else:
@@ -112,8 +144,9 @@ def refresh_transposed_operands():
 
 def bias_grad(bias):
     """fp32 .grad buffer of a bias (zero-initialised on first use): the `colsum` target of the kernel that PRODUCES the
-    Linear's output gradient (alpro_gather_cast / alpro_gemm epilogue), so dY is not read a second time for it."""
-    return grad_buffer(bias, zero=True)[0]
+    Linear's output gradient (alpro_gather_cast / alpro_gemm epilogue), so dY is not read a second time for it.  None for a frozen (or
+    absent) bias: the producer then forms no column sum."""
+    return grad_target(bias)
 
 
 def fused_grad_view(params):
@@ -136,27 +169,41 @@ def wgrad(dy_t, x_t, weight, bias, bias_done=False):
     """weight.grad += dy^T x ; bias.grad += colsum(dy) unless the producer of dy already did (bias_done).
     dy_t (M, N), x_t (M, K) operand-dtype activations.  16-bit operands: alpro_gemm_tn_acc reads both in place (split
     over tokens, fp32 atomics) and takes the bias gradient from the dY fragments it holds; fp32 (exact mode): transposed
-    copies + the NT GEMM, bias gradient fused into the transpose."""
-    if bias_done:
+    copies + the NT GEMM, bias gradient fused into the transpose.
+
+    Frozen parameters (requires_grad == False, read at every call): `.grad is None` is the contract, as after autograd's backward.
+    A frozen weight gets no buffer and no dW launch, a frozen bias asks for no column sum, and with both frozen nothing runs at all.
+    A frozen weight whose bias is trained: the column sums alone, with the bits the weight-gradient GEMM's own pass over dY gives them
+    (16-bit: alpro_colsum_tn restates that kernel's token split and order of additions; fp32: the sums are formed apart from the GEMM anyway)."""
+    if bias_done or not trainable(bias):
         bias = None
-    if bias is not None:
-        gb = grad_buffer(bias, zero=True)[0]
-    gw, existed = grad_buffer(weight, zero=True)
-    gw2 = gw.view(gw.shape[0], -1)
+    want_w = trainable(weight)
+    if not want_w and bias is None:
+        return
+    gb = grad_buffer(bias, zero=True)[0] if bias is not None else None
+    if want_w:
+        gw = grad_buffer(weight, zero=True)[0]
+        gw2 = gw.view(gw.shape[0], -1)
     if dy_t.dtype != torch.float32:
+        if not want_w:
+            hip.colsum_tn(dy_t, x_t.shape[1], gb)
+            return
         from alpro_amd import config as rt
         side = rt.wgrad_side_stream(dy_t.device)
         if side is None:
-            hip.gemm_tn_acc(dy_t, x_t, gw2, colsum=gb if bias is not None else None)  # bias gradient from the same pass over dy
+            hip.gemm_tn_acc(dy_t, x_t, gw2, colsum=gb)  # bias gradient from the same pass over dy
             return
         # side stream (alpro_amd.config, ALPRO_WGRAD_STREAM): behind everything the launch stream has queued so far (dy, x, the zeroed buffers)
         side.wait_stream(torch.cuda.current_stream(dy_t.device))
         with torch.cuda.stream(side):
-            hip.gemm_tn_acc(dy_t, x_t, gw2, colsum=gb if bias is not None else None)
+            hip.gemm_tn_acc(dy_t, x_t, gw2, colsum=gb)
         dy_t.record_stream(side)   # the launch stream's allocator may not hand these blocks out again before the side stream is done with them
         x_t.record_stream(side)
         return
-    dyT = hip.transpose(dy_t, colsum=gb if bias is not None else None)
+    if not want_w:
+        gb[:dy_t.shape[1]].add_(dy_t.sum(0, dtype=torch.float32))   # what hip.transpose(colsum=) adds in the reproducible mode, without the transpose
+        return
+    dyT = hip.transpose(dy_t, colsum=gb)
     hip.gemm(dyT, hip.transpose(x_t), out=gw2, out_dtype=torch.float32, residual=gw2)
 
 
@@ -246,7 +293,10 @@ class Anchor(torch.autograd.Function):
 
 
 def run_anchored(run, activations, params):
-    """Call `run` through autograd.  activations: tensors that may need gradients; params: nn.Parameters."""
+    """Call `run` through autograd.  activations: tensors that may need gradients; params: nn.Parameters.
+    Frozen parameters (requires_grad == False at this call) do not ride along, and the run's backward leaves their `.grad` alone -- None
+    unless an earlier step wrote it --, as autograd would; with no trainable parameter and no input that needs a gradient there is no
+    node at all and `run.forward` is the no-grad forward."""
     params = [p for p in params if p.requires_grad]
     need = torch.is_grad_enabled() and (any(torch.is_tensor(a) and a.requires_grad for a in activations) or len(params) > 0)
     if not need:

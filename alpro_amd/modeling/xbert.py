@@ -200,7 +200,8 @@ class BertLayer(nn.Module):
 
     def backward(self, sv, do32, do_t):
         """Gradients w.r.t. the layer's two output streams (fp32 residual copy, operand-dtype copy; either may be
-        None) -> (dh32, dh_t) for the layer input.  Parameter gradients accumulate into .grad."""
+        None) -> (dh32, dh_t) for the layer input.  Parameter gradients accumulate into .grad; a frozen parameter
+        (requires_grad == False now) gets none and costs nothing."""
         B, L, H, scale = sv["dims"]
         dt = sv["dt"]
         sa, so = self.attention.self, self.attention.output
@@ -213,7 +214,7 @@ class BertLayer(nn.Module):
             if dy_t is None:
                 dy_t, dy32 = dy32, None
             dx = torch.empty((M, D), dtype=torch.float32, device=dev)
-            g, b_ = tr.grad_buffer(ln.weight, zero=True)[0], tr.grad_buffer(ln.bias, zero=True)[0]
+            g, b_ = tr.grad_target(ln.weight), tr.grad_target(ln.bias)   # (None: frozen -- both None is the data-only LayerNorm backward)
             _, dx_t = hip.layernorm_bwd(dy_t, x, ln.weight, eps, dx, g, b_, dy2=dy32, accumulate=False,
                                         emit=dict(mode=hip.EMIT_ROWS, rows=M, dtype=dt, drop_p=hp if drop_seed else 0.0, drop_seed=drop_seed))
             return dx, dx_t
@@ -240,7 +241,9 @@ class BertLayer(nn.Module):
         Hd = sa.all_head_size
         lins = (sa.query, sa.key, sa.value)
         gw = gb = None
-        if dqkv.dtype != torch.float32:
+        # (a frozen third -- weight or bias -- leaves the fused form: each trainable parameter's gradient then comes from its own launch, written
+        # where its .grad lies -- inside FlatAdamW's flat buffer too --, and a frozen one gets neither a buffer nor a launch: tr.wgrad)
+        if dqkv.dtype != torch.float32 and all(tr.trainable(q) for lin in lins for q in (lin.weight, lin.bias)):
             for lin in lins:
                 tr.grad_buffer(lin.weight, zero=True)
                 tr.grad_buffer(lin.bias, zero=True)
@@ -480,9 +483,20 @@ class _BertRun:
         self.from_ids = encoder_embeds is None and self.parts is None
         self.saved = []
         lo, hi = m.encoder.layer_range(self.mode)
-        self.range = (lo, hi)
+        # the frozen prefix (tr.frozen_prefix; requires_grad is read now): leading stages -- the embeddings when this pass starts from ids, then the
+        # layers -- without a trainable parameter, provided no input (the fusion pass's text / video embeddings) needs a gradient: they run their
+        # no-grad forward (same dropout draws, nothing saved) and the backward ends at the first trainable layer's input
+        stages = ([list(emb.parameters())] if self.from_ids else []) + [list(m.encoder.layer[i].parameters()) for i in range(lo, hi)]
+        k = tr.frozen_prefix(stages, any(torch.is_tensor(a) and a.requires_grad for a in (encoder_embeds, video_pool)))
+        first = lo + max(k - (1 if self.from_ids else 0), 0)
+        self.range = (first, hi)
+        self.prefix = k > 0
         for i in range(lo, hi):
-            h32, h_t, sv = m.encoder.layer[i].forward_train(h32, h_t, kb, B, L, rows=self.out_rows if i == hi - 1 else None)
+            rows = self.out_rows if i == hi - 1 else None
+            if i < first:
+                h32, h_t = m.encoder.layer[i](h32, h_t, kb, B, L, rows=rows)
+                continue
+            h32, h_t, sv = m.encoder.layer[i].forward_train(h32, h_t, kb, B, L, rows=rows)
             self.saved.append(sv)
         return h32.view(B, L, -1) if self.out_rows is None else h32
 
@@ -493,6 +507,8 @@ class _BertRun:
         d32, d_t = (dout.reshape(B * L, -1) if self.out_rows is None else dout.reshape(self.out_rows.numel(), -1)).contiguous(), None
         for i in range(hi - 1, lo - 1, -1):
             d32, d_t = m.encoder.layer[i].backward(self.saved.pop(), d32, d_t)
+        if self.prefix:   # everything in front of layer `lo` is frozen and no input needs a gradient: the backward ends here
+            return None
         if self.parts is not None:   # per pool row, the sum over the sequences that used it (and of the 16-bit + fp32 parts of the gradient)
             if d_t is not None and d_t.dtype == torch.float32:
                 d32, d_t = d32 + d_t, None
@@ -502,19 +518,26 @@ class _BertRun:
         # embeddings: LN backward on word + type0 + pos, then scatter the row gradients into the tables
         emb = m.embeddings
         D = d32.shape[1]
+        tw, tp, tt = (tr.trainable(e.weight) for e in (emb.word_embeddings, emb.position_embeddings, emb.token_type_embeddings))
+        g, b_ = tr.grad_target(emb.LayerNorm.weight), tr.grad_target(emb.LayerNorm.bias)
+        if not (tw or tp or tt or g is not None or b_ is not None):
+            return None
         pre = (emb.word_embeddings.weight.detach()[self.ids.view(-1)] + emb.token_type_embeddings.weight.detach()[0]
                + emb.position_embeddings.weight.detach()[:L].repeat(B, 1)).contiguous()
         de = torch.empty_like(pre)
-        g, b_ = tr.grad_buffer(emb.LayerNorm.weight, zero=True)[0], tr.grad_buffer(emb.LayerNorm.bias, zero=True)[0]
         hip.layernorm_bwd(d_t, pre, emb.LayerNorm.weight, cfg.layer_norm_eps, de, g, b_, dy2=d32, accumulate=False,
                           drop_p=self.emb_drop[0], drop_seed=self.emb_drop[1])
-        gw = tr.grad_buffer(emb.word_embeddings.weight, zero=True)[0] if emb.word_embeddings.weight.grad is None else emb.word_embeddings.weight.grad
-        pad = emb.word_embeddings.padding_idx   # nn.Embedding(padding_idx): the pad row's lookup gradient stays zero (xbert.py:171)
-        hip.scatter_add_rows(de, self.ids.view(-1), gw, skip_idx=-1 if pad is None else int(pad))
-        gp = tr.grad_buffer(emb.position_embeddings.weight, zero=True)[0] if emb.position_embeddings.weight.grad is None else emb.position_embeddings.weight.grad
-        hip.scatter_add_rows(de, None, gp, idx_mod=L)
-        gt = tr.grad_buffer(emb.token_type_embeddings.weight, zero=True)[0] if emb.token_type_embeddings.weight.grad is None else emb.token_type_embeddings.weight.grad
-        gt[0].add_(de.sum(0))
+        # a frozen table skips its scatter / sum
+        if tw:
+            gw = tr.grad_buffer(emb.word_embeddings.weight, zero=True)[0] if emb.word_embeddings.weight.grad is None else emb.word_embeddings.weight.grad
+            pad = emb.word_embeddings.padding_idx   # nn.Embedding(padding_idx): the pad row's lookup gradient stays zero (xbert.py:171)
+            hip.scatter_add_rows(de, self.ids.view(-1), gw, skip_idx=-1 if pad is None else int(pad))
+        if tp:
+            gp = tr.grad_buffer(emb.position_embeddings.weight, zero=True)[0] if emb.position_embeddings.weight.grad is None else emb.position_embeddings.weight.grad
+            hip.scatter_add_rows(de, None, gp, idx_mod=L)
+        if tt:
+            gt = tr.grad_buffer(emb.token_type_embeddings.weight, zero=True)[0] if emb.token_type_embeddings.weight.grad is None else emb.token_type_embeddings.weight.grad
+            gt[0].add_(de.sum(0))
         return None
 
 
@@ -553,8 +576,8 @@ class BertLMPredictionHead(nn.Module):
         alpro_models.py:368-371 as ONE autograd node -- alpro_softmax_xent writes (softmax - onehot)/n straight in the
         operand dtype, so the (B*Lt, vocab) fp32 gradient is never materialised.  NaN when no label is valid, like the
         reference."""
-        run = _LMHeadRun(self, labels.reshape(-1).contiguous(), ignore_index)
         need = torch.is_grad_enabled() and (hidden_states.requires_grad or any(p.requires_grad for p in self.parameters()))
+        run = _LMHeadRun(self, labels.reshape(-1).contiguous(), ignore_index, need_grad=need)
         if need:
             logits, loss = tr.run_anchored(run, [hidden_states], list(self.parameters()))
         else:
@@ -566,8 +589,9 @@ class BertLMPredictionHead(nn.Module):
 class _LMHeadRun:
     """Forward/backward of BertLMPredictionHead for tr.Anchor; the decoder weight is the word-embedding table."""
 
-    def __init__(self, head, labels=None, ignore_index=-100):
-        self.h, self.labels, self.ignore = head, labels, ignore_index
+    def __init__(self, head, labels=None, ignore_index=-100, need_grad=None):
+        # need_grad: a parameter OR the hidden states need a gradient (a frozen head still passes d(hidden) on); None: decided from the parameters
+        self.h, self.labels, self.ignore, self.need_grad = head, labels, ignore_index, need_grad
 
     def forward(self, hidden):
         hd, dt = self.h, rt.compute_dtype()
@@ -582,7 +606,7 @@ class _LMHeadRun:
         if self.labels is None:
             return logits.view(*self.shape[:-1], -1)
         inv_n = (1.0 / (self.labels != self.ignore).sum().to(torch.float32)).reshape(1)
-        want_grad = any(p.requires_grad for p in hd.parameters())
+        want_grad = self.need_grad if self.need_grad is not None else any(p.requires_grad for p in hd.parameters())
         # fp16 operands: (softmax - onehot) / n is written in 16 bits NOW, so it must already carry the loss scale of the coming
         # backward (alpro_amd.amp); backward() divides the incoming d(loss) by the same value.
         self.pre_scale = rt.armed_loss_scale(logits.device) if want_grad else None
@@ -626,16 +650,26 @@ class _LMHeadRun:
             dn = dn * up
             n_op = n_op * up
         # decoder weight is the (tied) word-embedding table: dW (V, H) += dl^T n ; bias += colsum(dl)
-        gw = tr.grad_buffer(hd.decoder.weight, zero=True)[0]
-        cs = torch.zeros(Vp, dtype=torch.float32, device=dl.device)
-        if dt != torch.float32:
-            hip.gemm_tn_acc(dl[:, :V], n_op, gw, colsum=cs)
-        else:
-            dlT = hip.transpose(dl, colsum=cs)
-            hip.gemm(dlT[:V], hip.transpose(n_op), out=gw, out_dtype=torch.float32, residual=gw)
-        tr.add_grad(hd.bias, cs[:V] if up is None else cs[:V] * up)
+        # (frozen table / frozen vocabulary bias, requires_grad read now: no buffer, and with the table frozen no V x H GEMM -- a trainable bias alone
+        # takes its column sums from alpro_colsum_tn, with that GEMM's bits: tr.wgrad)
+        t_w, t_b = tr.trainable(hd.decoder.weight), tr.trainable(hd.bias)
+        if t_w or t_b:
+            cs = torch.zeros(Vp, dtype=torch.float32, device=dl.device) if t_b else None
+            if dt != torch.float32 and t_w:
+                gw = tr.grad_buffer(hd.decoder.weight, zero=True)[0]
+                hip.gemm_tn_acc(dl[:, :V], n_op, gw, colsum=cs)
+            elif dt != torch.float32:
+                hip.colsum_tn(dl[:, :V], n_op.shape[1], cs)
+            elif t_w:
+                gw = tr.grad_buffer(hd.decoder.weight, zero=True)[0]
+                dlT = hip.transpose(dl, colsum=cs)
+                hip.gemm(dlT[:V], hip.transpose(n_op), out=gw, out_dtype=torch.float32, residual=gw)
+            else:
+                cs[:dl.shape[1]].add_(dl.sum(0, dtype=torch.float32))
+            if t_b:
+                tr.add_grad(hd.bias, cs[:V] if up is None else cs[:V] * up)
         dg = torch.empty_like(self.g)
-        gw, gb = tr.grad_buffer(t.LayerNorm.weight, zero=True)[0], tr.grad_buffer(t.LayerNorm.bias, zero=True)[0]
+        gw, gb = tr.grad_target(t.LayerNorm.weight), tr.grad_target(t.LayerNorm.bias)
         hip.layernorm_bwd(dn, self.g, t.LayerNorm.weight, hd.config.layer_norm_eps, dg, gw, gb, accumulate=False)
         du = hip.gelu_bwd(hip.gather_cast(dg, dt), self.u)
         tr.wgrad(du, self.x, t.dense.weight, t.dense.bias)

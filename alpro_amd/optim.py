@@ -559,6 +559,13 @@ class FlatAdamW:
                 f["lp"] = torch.empty(f["n"], dtype=dt, device=f["p"].device)
                 hip.cast(f["p"], dt, out=f["lp"])
             lp = f["lp"]
+        # Parameters frozen AFTER the flat buffers were built (requires_grad set to False for an epoch, read now): their slice of the gradient buffer
+        # holds the zeros zero_grad() left -- the backward writes nothing for a frozen parameter -- and torch.optim skips a parameter whose .grad is
+        # None.  The one-pass kernel walks whole ranges and would still apply weight decay and decay the moments, so the slices' value, moments
+        # (and 16-bit mirror) are put back behind it: the parameter does not move and resumes from its old moments when it is unfrozen.  A
+        # parameter frozen for good is best left out when the optimizer is built (it then never enters the buffers).
+        held = [(a, e, f["p"][a:e].clone(), f["m"][a:e].clone(), f["v"][a:e].clone())
+                for a, e in self._merge([self._span[id(p)] for p in f["live"] if not p.requires_grad])]
         if grouped:   # still ONE pass and one launch: the hyper-parameters travel as a segment table in the kernel arguments
             hip.adamw_step_groups(f["p"], f["g"], f["m"], f["v"], self._segments(self.step_count), norm, float(self.max_grad_norm or 0.0), 1.0 / world,
                                   dyn_state=sc.state if sc is not None else None, grads_scaled=self._grads_scaled, zero_grad=self.fused_zero_grad, lp=lp)
@@ -566,6 +573,12 @@ class FlatAdamW:
             hip.adamw_step(f["p"], f["g"], f["m"], f["v"], lr, b1, b2, grp["eps"], grp["weight_decay"], step_size, norm,
                            float(self.max_grad_norm or 0.0), 1.0 / world, dyn_state=sc.state if sc is not None else None,
                            grads_scaled=self._grads_scaled, correct_bias=grp["correct_bias"], zero_grad=self.fused_zero_grad, lp=lp)
+        for a, e, hp, hm, hv in held:
+            f["p"][a:e].copy_(hp)
+            f["m"][a:e].copy_(hm)
+            f["v"][a:e].copy_(hv)
+            if lp is not None:
+                lp[a:e].copy_(hp)
         self._g_clean = self.fused_zero_grad
         self._clean_epoch = _backward_epoch()
         if sc is not None:  # overflow -> the kernel skipped the update; the schedule halves / grows the scale on the device

@@ -367,6 +367,11 @@ int alpro_layernorm_bwd(const void* dy, int dy_dtype, int64_t ld_dy, const float
                         uint32_t drop_seed, void* workspace, size_t workspace_bytes, void* stream);
 /* drop_p > 0: the incoming gradient dy (+dy2) is first multiplied by the dropout mask hash(seed, m*D+n)/(1-p) that the
  * forward applied to this LayerNorm's OUTPUT (embedding dropout). */
+/* dgamma == dbeta == NULL (both entry points): gamma and beta are frozen.  The data-only form of the kernel runs: the same dx rows and the
+ * same emitted rows bit for bit (every map mode, emit mode, dropout, accumulate, dy2, emit_extra_cls), but no column sums -- none kept in
+ * registers, no LDS, no partials in the workspace, no atomics, no reduce launch (the workspace is then used for the CLS frame terms of
+ * ALPRO_MAP_FRAME_TOKENS only).  Exactly one of the two NULL is an error, and so is the NULL pair with emit_colsum_pre != NULL: a caller
+ * that still wants colsum_pre runs the full kernel into a throw-away dgamma / dbeta pair. */
 
 /* alpro_layernorm_bwd that ALSO emits the finished gradient row as the `dy_dtype` operand row(s) of the GEMMs that consume it next --
  * what a following alpro_gather_cast would produce from re-reading dx (autograd has no counterpart: the reference materialises the
@@ -459,6 +464,11 @@ int alpro_gemm_tn_acc_ws(const void* A, int64_t lda, const void* B, int64_t ldb,
 
 /* out[n] (fp32) += sum_m A[m, n]: bias gradients. */
 int alpro_colsum_acc(const void* A, int64_t lda, float* out, int dtype, int M, int N, void* stream);
+/* colsum[n] += sum_m A[m, n] with the BITS alpro_gemm_tn_acc_ws(A (M, N), B (M, K), ..., colsum, workspace) gives its bias gradient -- the same
+ * token ranges (alpro_gemm_tn_ranges under this stream's CU budget), the same turns of the ceil(K / 256) k-tiles, the same order of additions --
+ * without the weight-gradient GEMM: the bias gradient of a Linear whose weight is frozen.  16-bit A; workspace: 16-byte aligned, at least
+ * ranges * ceil(K / 256) * (N rounded up to 32) floats (alpro_gemm_tn_workspace_bytes(M, N, K) always suffices), scratch in stream order. */
+int alpro_colsum_tn(const void* A, int64_t lda, int dtype, int M, int N, int K, float* colsum, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Masked-LM cross entropy (alpro_models.py:368-371: CrossEntropyLoss over (B*Lt, vocab), ignore_index -100):
  * loss_rows[m] = logsumexp(logits[m]) - logits[m, label] (0 for ignored rows) and, if dlogits != NULL,
