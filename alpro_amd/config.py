@@ -287,6 +287,53 @@ def set_defer_temporal_add(v):
     _defer_tadd[0] = bool(v)
 
 
+# Recompute the ViT blocks' activations in backward.  Off (default): the anchored visual backward keeps every activation
+# of the step (~37 KB per token row and block).  On: each trainable block keeps its input, its three drop-path scale vectors and its two
+# attention-dropout seeds (~3 KB per row) and its forward_train body runs once more right before its backward -- the same kernels on the same
+# operands, so outputs, gradients and both random streams are those of the stored step bit for bit, at the price of one more ViT training forward.
+# ALPRO_RECOMPUTE = 0 | 1 (default 0), read at every _VisualRun.forward.  `video_enc_cfg.gradient_checkpointing` does NOT set it.
+def _recompute_from_env():
+    v = os.environ.get("ALPRO_RECOMPUTE", "0").strip()
+    if v not in ("0", "1"):
+        raise ValueError("ALPRO_RECOMPUTE=%r: expected 0 (keep every ViT block activation, the default) or 1 (recompute them in backward)" % v)
+    return v == "1"
+
+
+_recompute = [_recompute_from_env()]
+
+
+def recompute_blocks():
+    return _recompute[0]
+
+
+def set_recompute(flag):
+    _recompute[0] = bool(flag)
+
+
+class use_recompute:
+    """Context manager: `with use_recompute(True): loss = model(batch); loss.backward()` (the switch is read by the forward; the backward
+    follows what its forward kept)."""
+
+    def __init__(self, flag):
+        self.flag = flag
+
+    def __enter__(self):
+        self.prev = recompute_blocks()
+        set_recompute(self.flag)
+
+    def __exit__(self, *a):
+        set_recompute(self.prev)
+
+
+def wgrad_side_event(device):
+    """An event behind every weight gradient launched so far on the side stream of the current launch stream, or None if there is none."""
+    if device.type != "cuda":
+        return None
+    key = (device.index if device.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(device).cuda_stream)
+    ent = _WGRAD_SIDE.get(key)
+    return ent[0].record_event() if (ent is not None and ent[1]) else None
+
+
 def set_cls_precise(v):
     _cls_precise[0] = v.lower() if isinstance(v, str) else ("1" if v else "0")
 

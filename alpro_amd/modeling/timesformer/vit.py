@@ -380,19 +380,21 @@ class Block(nn.Module):
         (vit.py:165-212); eval mode only (no drop-path).  Returns the block output's CLS rows, (B, D) fp32."""
         return self._forward(x, B, T, cls_only=True)
 
-    def _forward(self, x, B, T, save=False, cls_only=False, drop_masks=None):
+    def _forward(self, x, B, T, save=False, cls_only=False, drop_masks=None, replay=None, cls_precise=None):
         """The divided space-time block (vit.py:146-212), every stage stated once.  The residual stream goes
             x --temporal branch--> xt --spatial branch--> x2 --MLP--> out
         and the three entry points differ in where those four live and in what is kept:
             forward        all four ARE x; with the merged projection xt is never written (its add rides in the add + norm2 kernel)
             forward_train  save: a fresh tensor each, q | k | v, the log-sum-exp rows and gelu' kept -> (out, saved)
-            forward_cls    cls_only: as forward up to the spatial attention, the rest on the CLS rows -> their (B, D) output rows"""
-        dt = rt.compute_dtype()
+            forward_cls    cls_only: as forward up to the spatial attention, the rest on the CLS rows -> their (B, D) output rows
+        replay (Block.replay): the kept subset of an earlier forward_train's saved dict; operand dtype, projection form, drop-path scales and
+        attention-dropout seeds are taken from it and nothing is drawn.  cls_precise: the precise-CLS decision of that earlier pass (None: read now)."""
+        dt = replay["dt"] if replay is not None else rt.compute_dtype()
         S, D = x.shape[1], x.shape[2]
         N = (S - 1) // T
         H = self.attn.num_heads
         ta, sa, fc, mlp, dev, f32 = self.temporal_attn, self.attn, self.temporal_fc, self.mlp, x.device, torch.float32
-        merged = self.merge_temporal_proj
+        merged = replay["merged"] if replay is not None else self.merge_temporal_proj
         xf = x.view(B * S, D)
         if cls_only:   # eval mode only: no drop-path mask and no dropout seed is drawn (the seed stream of later BERT layers does not shift)
             drop_t = drop_s = drop_m = None
@@ -401,9 +403,9 @@ class Block(nn.Module):
         else:
             drop_t, drop_s, drop_m = drop_masks if drop_masks is not None else (self._drop(B * N, dev), self._drop(B * T, dev), self._drop(B, dev))
             rs_t, rs_s, rs_m = (dict(row_scale=d, row_scale_group=g) for d, g in ((drop_t, T), (drop_s, N + 1), (drop_m, S)))
-            seeds = ap_t, seed_t, ap_s, seed_s = self._attn_drop_seeds()   # the backward regenerates the masks from these
+            seeds = ap_t, seed_t, ap_s, seed_s = replay["attn_drop"] if replay is not None else self._attn_drop_seeds()   # the backward regenerates the masks from these
         # precise CLS rows, decided once: off (cp False) | on the launch stream (cp, side None) | on the side stream (side)
-        cp = merged and not cls_only and rt.cls_precise(dt)
+        cp = merged and not cls_only and (rt.cls_precise(dt) if cls_precise is None else cls_precise)
         side = _ClsSide.get(dev) if (cp and rt.cls_stream(save) and x.is_cuda) else None
         ev_mid = None
         if side is not None:
@@ -509,6 +511,26 @@ class Block(nn.Module):
             return out
         return out, dict(x=x, dims=(B, T, N, S, D, H), dt=dt, drop_t=drop_t, drop_s=drop_s, drop_m=drop_m, attn_drop=seeds, merged=merged, u_tiled=u_tiled,
                          h=h, qkv_t=qkv_t, a_t=a_t, lse_t=lse_t, pr=pr, xt=xt, hs=hs, qkv_s=qkv_s, a_s=a_s, lse_s=lse_s, x2=x2, h2=h2, u=u, f1=f1)
+
+    SLIM_KEYS = ("x", "drop_t", "drop_s", "drop_m", "attn_drop", "dims", "dt", "merged", "u_tiled")
+
+    @staticmethod
+    def slim_saved(sv):
+        """What recomputation keeps of forward_train's saved dict (alpro_amd.config.recompute_blocks): the block input, the three drop-path scale
+        vectors, the attention-dropout tuple and the scalars -- a dict of its own, so clearing `sv` releases every other activation and leaves this
+        one whole.  Pure: no device work."""
+        return {k: sv[k] for k in Block.SLIM_KEYS}
+
+    def replay(self, slim, W, cls_precise=None):
+        """slim_saved(...) of an earlier forward_train -> the full saved dict again, by running the same _forward body on the kept input with the
+        kept drop-path scales and dropout seeds.  Draws nothing: no dropout seed, no torch RNG, no pre-sampled mask is touched, and the module's
+        train / eval state is not read.  The precise-CLS chain runs again where the first pass ran it (launch stream or its side stream) and is
+        joined here, before anyone reads the rebuilt x2 and before the block output, which nobody needs, is released.
+        The operand copies (16-bit weights, merged projection) are the step's: parameters must not have changed since the first pass."""
+        B, T = slim["dims"][0], slim["dims"][1]
+        out, sv = self._forward(slim["x"], B, T, save=True, drop_masks=(slim["drop_t"], slim["drop_s"], slim["drop_m"]), replay=slim, cls_precise=cls_precise)
+        _ClsSide.join(out.device)
+        return sv
 
     def _wt(self, name, lin, dt):
         return tr.transposed_operand(self._ops, name + "^T", lin.weight, dt)
@@ -962,11 +984,14 @@ class TimeSformer(nn.Module):
         self.use_grad_ckpt = model_cfg['gradient_checkpointing']
         if self.use_grad_ckpt:
             # config_release/timesformer_divst_8x32_224_k600_gc.json:9.  The reference re-runs each Block in backward to fit 16-40 GB devices
-            # (vit.py:366-370); this build keeps every activation a step needs (64 GB at B = 64 x 8 frames of the 288 GB) and never recomputes:
-            # the flag is accepted for config compatibility and has NO effect -- said once, not silently
+            # (vit.py:366-370) -- and loses the blocks' parameter gradients doing so, so "what the reference does" is no
+            # contract.  The flag is accepted for config compatibility and has NO effect -- said once, not silently; recomputation
+            # is a runtime switch of its own (alpro_amd.config.recompute_blocks) and the warning names it
             import warnings
-            warnings.warn("alpro_amd: gradient_checkpointing=true is accepted and ignored -- activations are kept in HBM (288 GB per MI355X; "
-                          "B=64 x 8 frames peaks at 64 GB), no block is recomputed in backward", RuntimeWarning, stacklevel=2)
+            warnings.warn("alpro_amd: gradient_checkpointing=true is accepted and ignored -- by default activations are kept in HBM (288 GB per MI355X; "
+                          "B=64 x 8 frames peaks at 64 GB) and no block is recomputed in backward.  To recompute the ViT blocks' activations in backward "
+                          "(bit for bit the same step, one block's activations live at a time) set ALPRO_RECOMPUTE=1 or use alpro_amd.config.use_recompute(True)",
+                          RuntimeWarning, stacklevel=2)
         self.attention_type = 'divided_space_time'
         self.num_classes = 400
         self.input_format = input_format
@@ -1065,6 +1090,10 @@ class _VisualRun:
         if self.embed_frozen:
             m._last_rows = None   # (the patch rows are the weight gradient's operand: nobody reads them)
         self.saved = []
+        # recomputation (alpro_amd.config.recompute_blocks, read NOW like requires_grad): every trainable block's saved dict is cut down to what
+        # Block.replay needs as soon as the block is through -- one block's activations are live at a time -- and backward() rebuilds it
+        self.recompute = rt.recompute_blocks()
+        self.cp = rt.cls_precise(rt.compute_dtype())   # (the replay takes the first pass's precise-CLS decision, not the one in force at backward time)
         if B * N != B * T and B * T != B:  # (the table is keyed by row count: the three counts must differ, else draw per call)
             sample_drop_paths(m.blocks, B, T, N, tok.device)
         if self.nfro:
@@ -1074,6 +1103,11 @@ class _VisualRun:
         for blk in m.blocks[self.nfro:]:
             tok, sv = blk.forward_train(tok, B, T, W)
             blk._presampled = None
+            if self.recompute:
+                _ClsSide.join(tok.device)   # a precise-CLS chain on its side stream still writes x2's CLS rows: it is through before x2 is released
+                sv, full = Block.slim_saved(sv), sv
+                full.clear()
+                del full
             self.saved.append(sv)
         _ClsSide.join(tok.device)
         self.tok = tok
@@ -1126,8 +1160,19 @@ class _VisualRun:
         if overlap:
             dist.grads_final(all_but=list(self.enc.parameters()))
         group_hi, group_rule = nb, []
+        marks = {}
         for j in range(nb - 1, nfro - 1, -1):   # block j; blocks below nfro are the frozen prefix: the backward ends at block nfro's input
             blk, sv = m.blocks[j], self.saved[j - nfro]
+            if self.recompute:
+                # rebuilt right before its backward and cleared right behind it; block j - 1 hands over its drop-path scales (emit_for) from its
+                # kept dict and is replayed only when its turn comes.  The weight-gradient side stream holds the operands of the blocks behind us
+                # (record_stream) until it has read them: the host lets it fall at most two blocks behind, so that what it is done with can be
+                # handed out again instead of piling up beside the replayed block
+                ev = marks.pop(j + 2, None)
+                if ev is not None:
+                    ev.synchronize()
+                sv = blk.replay(sv, self.Wg, cls_precise=self.cp)
+                self.saved[j - nfro] = None
             sv["ws"] = ws[j]
             sv["defer_product_rule"] = banked and bank.all_trainable(j)   # (a block with a frozen member applies the rule itself)
             if sv["defer_product_rule"]:
@@ -1141,6 +1186,8 @@ class _VisualRun:
                     dist.grads_final(params=[p for b in m.blocks[j:group_hi] for p in b.parameters()] + (list(m.norm.parameters()) if group_hi == nb else []))
                 group_hi, group_rule = j, []
             sv.clear()
+            if self.recompute:
+                marks[j] = rt.wgrad_side_event(dtok.device)
         if not self.embed_frozen:
             m._embed_backward(self.rows, dtok, B, T, N, self.Wg)
         self.saved = self.rows = self.tok = None
