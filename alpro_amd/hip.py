@@ -17,6 +17,9 @@ POOL_MODES = {"mean": 0, "max": 1, "lse": 2}   # alpro_clip_pool (run_video_qa.p
 MAP_IDENTITY, MAP_SKIP_CLS, MAP_FRAME_TOKENS, MAP_PATCH_EMBED = 0, 1, 2, 3
 ADD_IDENTITY, ADD_PRE_SPATIAL, ADD_PRE_MLP, ADD_PRE_TEMPORAL = 0, 1, 2, 3
 EMIT_NONE, EMIT_ROWS, EMIT_FRAME, EMIT_SKIP_CLS = 0, 1, 2, 3
+# ALPRO_AUG_*: the op codes of alpro_augment_stage, by the names randaugment.py's func_dict gives them (no Equalize)
+AUG_OPS = {"Identity": 0, "HorizontalFlip": 1, "Brightness": 2, "Contrast": 3, "Sharpness": 4, "Color": 5, "Solarize": 6, "Posterize": 7,
+           "TranslateX": 8, "TranslateY": 9, "ShearX": 10, "ShearY": 11, "Rotate": 12}
 POOL_TEMPORAL, POOL_SPATIAL, POOL_NONE = 0, 1, 2   # ALPRO_POOL_*: the pooling modes of TimeSformer.forward_features (alpro_vit_final_pool_mode)
 
 _TORCH_DTYPE = {F32: torch.float32, BF16: torch.bfloat16, F16: torch.float16}
@@ -28,7 +31,7 @@ EXPORTS = ["alpro_hip_last_error", "alpro_hip_abi_version", "alpro_hip_set_optio
            "alpro_layernorm_bwd", "alpro_transpose", "alpro_transpose_batch", "alpro_gelu_bwd", "alpro_cls_mean_bwd", "alpro_scatter_add_rows", "alpro_gather_cast", "alpro_sumsq", "alpro_adamw_step", "alpro_gemm_tn_acc", "alpro_gemm_tn_acc_ws", "alpro_gemm_tn_workspace_bytes", "alpro_gemm_tn_ranges", "alpro_colsum_acc", "alpro_colsum_tn", "alpro_softmax_xent", "alpro_vtc_loss_fwd", "alpro_vtc_loss_bwd", "alpro_prepare_clips", "alpro_loss_scale_update", "alpro_add_layernorm_fwd", "alpro_layernorm_bwd_emit", "alpro_gemm_batch", "alpro_tproj_small", "alpro_attn_cls_fwd", "alpro_gemm_rows_f32", "alpro_gather_seq_fwd", "alpro_gather_seq_bwd", "alpro_scatter_add_rows_ordered",
            "alpro_hip_sched_workspace_bytes", "alpro_hip_set_sched_workspace", "alpro_hip_release_stream", "alpro_gemm_qkv_tattn", "alpro_add_layernorm_pre_mlp2", "alpro_adamw_step_lp",
            "alpro_gemm_rows_f32_relu_mask", "alpro_clip_pool", "alpro_adamw_step_groups", "alpro_attn_temporal_fwd_drop", "alpro_attn_temporal_bwd_drop",
-           "alpro_vit_final_pool_mode", "alpro_vit_final_pool_mode_bwd"]
+           "alpro_vit_final_pool_mode", "alpro_vit_final_pool_mode_bwd", "alpro_augment_stage", "alpro_augment_stats"]
 
 
 class GemmDesc(ctypes.Structure):
@@ -149,6 +152,8 @@ def load():
     lib.alpro_gather_seq_fwd.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
     lib.alpro_gather_seq_bwd.argtypes = [vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
     lib.alpro_prepare_clips.argtypes = [vp, i32, vp, f32, ctypes.POINTER(f32), ctypes.POINTER(f32), vp, vp, vp, i32, i32, i32, i32, vp]
+    lib.alpro_augment_stage.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
+    lib.alpro_augment_stats.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
     lib.alpro_vtc_loss_fwd.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
     lib.alpro_vtc_loss_bwd.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     if lib.alpro_hip_abi_version() != ABI_VERSION:
@@ -1109,3 +1114,65 @@ def prepare_clips(raw, mean, std, scale, boxes=None, want_crop=True):
     _check(lib.alpro_prepare_clips(_ptr(raw), int(raw.dtype == torch.uint8), _ptr(boxes) if crop is not None else None, float(scale), m3, s3,
                                    _ptr(vis), _ptr(crop), _ptr(ctx), B, T, H, W, _stream()), "alpro_prepare_clips")
     return vis, crop, ctx
+
+
+def _augment_args(who, src, ops, args, crop, out_hw):
+    """Shared refusals of augment_stage / augment_stats; returns (B, T, Hs, Ws, Hc, Wc)."""
+    if not isinstance(src, torch.Tensor) or not src.is_cuda:
+        raise RuntimeError("%s needs a device tensor, got %s (no CPU fallback)" % (who, getattr(src, "device", type(src).__name__)))
+    if src.dtype != torch.uint8:
+        raise RuntimeError("%s needs uint8 pixels, got %s" % (who, src.dtype))
+    if src.dim() != 5 or src.shape[2] != 3:
+        raise RuntimeError("%s needs (B, T, 3, H, W) clips, got shape %s" % (who, tuple(src.shape)))
+    if not src.is_contiguous():
+        raise RuntimeError("%s needs a contiguous tensor, got strides %s for shape %s" % (who, tuple(src.stride()), tuple(src.shape)))
+    B, T, _, Hs, Ws = src.shape
+    Hc, Wc = (Hs, Ws) if out_hw is None else (int(out_hw[0]), int(out_hw[1]))
+    if Hc < 1 or Hc > Hs or Wc < 1 or Wc > Ws:
+        raise RuntimeError("%s: crop %d x %d does not fit the %d x %d frame" % (who, Hc, Wc, Hs, Ws))
+    if crop is None and (Hc, Wc) != (Hs, Ws):
+        raise RuntimeError("%s: output %d x %d differs from the frame %d x %d but there are no crop offsets" % (who, Hc, Wc, Hs, Ws))
+    _dev(ops, torch.int32)
+    _dev(args, torch.float64)
+    if ops.numel() != B or args.numel() != 2 * B:
+        raise RuntimeError("%s: ops must hold %d codes and args %d values, got %d and %d" % (who, B, 2 * B, ops.numel(), args.numel()))
+    if crop is not None:
+        _dev(crop, torch.int32)
+        if crop.numel() != 2 * B:
+            raise RuntimeError("%s: crop offsets must be (%d, 2), got shape %s" % (who, B, tuple(crop.shape)))
+    return B, T, Hs, Ws, Hc, Wc
+
+
+def augment_buffers(B, T, device):
+    """The per-frame workspace of the augmentation stages: (sums (B*T, 3) int64, tables (B*T, 256) uint8)."""
+    return torch.zeros(B * T, 3, dtype=torch.int64, device=device), torch.zeros(B * T, 256, dtype=torch.uint8, device=device)
+
+
+def augment_stats(src, ops, args, sums, tables, crop=None, out_hw=None):
+    """alpro_augment_stats: exact channel sums and Contrast tables of the frames whose clip's op is Contrast, over the crop window."""
+    lib = load()
+    B, T, Hs, Ws, Hc, Wc = _augment_args("augment_stats", src, ops, args, crop, out_hw)
+    _dev(sums, torch.int64)
+    _dev(tables, torch.uint8)
+    if sums.numel() != B * T * 3 or tables.numel() != B * T * 256:
+        raise RuntimeError("augment_stats: sums / tables must be (%d, 3) / (%d, 256), got %s / %s" % (B * T, B * T, tuple(sums.shape), tuple(tables.shape)))
+    _check(lib.alpro_augment_stats(_ptr(src), _ptr(crop), _ptr(ops), _ptr(args), _ptr(sums), _ptr(tables), B, T, Hs, Ws, Hc, Wc, _stream()), "alpro_augment_stats")
+    return sums, tables
+
+
+def augment_stage(src, ops, args, tables, dst=None, crop=None, out_hw=None):
+    """alpro_augment_stage: one op per clip (ops (B) int32 AUG_OPS codes, -1 = copy; args (B, 2) fp64; both on the device) applied to every
+    frame of src (B, T, 3, Hs, Ws) uint8 -> dst (B, T, 3, Hc, Wc) uint8, read through the per-clip crop window crop (B, 2) int32 {top, left}
+    when out_hw = (Hc, Wc) is smaller than the frame.  tables: what augment_stats wrote for the same arguments (Contrast clips read it)."""
+    lib = load()
+    B, T, Hs, Ws, Hc, Wc = _augment_args("augment_stage", src, ops, args, crop, out_hw)
+    _dev(tables, torch.uint8)
+    if tables.numel() != B * T * 256:
+        raise RuntimeError("augment_stage: tables must be (%d, 256), got shape %s" % (B * T, tuple(tables.shape)))
+    if dst is None:
+        dst = torch.empty((B, T, 3, Hc, Wc), dtype=torch.uint8, device=src.device)
+    _dev(dst, torch.uint8)
+    if tuple(dst.shape) != (B, T, 3, Hc, Wc) or not dst.is_contiguous():
+        raise RuntimeError("augment_stage: dst must be a contiguous %s tensor, got shape %s" % ((B, T, 3, Hc, Wc), tuple(dst.shape)))
+    _check(lib.alpro_augment_stage(_ptr(src), _ptr(dst), _ptr(crop), _ptr(ops), _ptr(args), _ptr(tables), B, T, Hs, Ws, Hc, Wc, _stream()), "alpro_augment_stage")
+    return dst

@@ -285,6 +285,32 @@ int alpro_patchify(const float* img, void* out, int dtype, int BT, int C, int Hi
 int alpro_prepare_clips(const void* raw, int raw_is_u8, const int* boxes, float scale, const float* mean3, const float* std3, float* visual,
                         float* crop, float* context, int B, int T, int H, int W, void* stream);
 
+/* Clip augmentation in front of alpro_prepare_clips (still ABI 22: additions only): ONE op stage of TemporalConsistentRandomAugment
+ * (src/datasets/randaugment.py:323-361) over a whole batch, with VideoRandomSquareCrop (src/datasets/data_utils.py:310-336) on the read side.
+ *   src (B, T, 3, Hs, Ws) uint8 -> dst (B, T, 3, Hc, Wc) uint8, dst must not overlap src.
+ *   crop_offsets (B, 2) int32 {top, left} on the DEVICE, NULL = none (then Hc == Hs and Wc == Ws); the kernel clamps them into the frame.
+ *   ops (B) int32 on the DEVICE: the ALPRO_AUG_* code of each clip, every frame of a clip gets the same; -1 (or an unknown code) copies.
+ *   args (B, 2) fp64 on the DEVICE: Brightness / Contrast / Sharpness / Color {f}, Solarize {t}, Posterize {bits}, TranslateX / Y {offset},
+ *   ShearX / Y {s}, Rotate {cos d, sin d}; fp32 ops round them to fp32 first.
+ *   tables (B * T, 256) uint8: the Contrast tables alpro_augment_stats wrote for THIS src, crop_offsets, ops and args (read for Contrast clips only).
+ * Every op maps uint8 to uint8 as the reference's function does on a frame: geometric ops are dst(x, y) = src(sx, sy) over the four taps around
+ * the fp32 source position, a tap outside the (cropped) image holding 128, rounded to nearest; the rotation centre and the shear origin are
+ * those of the cropped image.  Source positions are floating point, not the 1/32-pixel fixed point of OpenCV's warpAffine.  Sharpness values
+ * that leave 0..255 (f > 1) are clamped (the reference's cast is platform-defined there).  No Equalize. */
+enum {
+  ALPRO_AUG_IDENTITY = 0, ALPRO_AUG_HFLIP = 1, ALPRO_AUG_BRIGHTNESS = 2, ALPRO_AUG_CONTRAST = 3, ALPRO_AUG_SHARPNESS = 4, ALPRO_AUG_COLOR = 5,
+  ALPRO_AUG_SOLARIZE = 6, ALPRO_AUG_POSTERIZE = 7, ALPRO_AUG_TRANSLATE_X = 8, ALPRO_AUG_TRANSLATE_Y = 9, ALPRO_AUG_SHEAR_X = 10,
+  ALPRO_AUG_SHEAR_Y = 11, ALPRO_AUG_ROTATE = 12
+};
+int alpro_augment_stage(const uint8_t* src, uint8_t* dst, const int32_t* crop_offsets, const int32_t* ops, const double* args,
+                        const uint8_t* tables, int B, int T, int Hs, int Ws, int Hc, int Wc, void* stream);
+/* What Contrast needs before its stage, for the frames of the clips whose op is ALPRO_AUG_CONTRAST (other frames are left alone): sums
+ * (B * T, 3) uint64 = the exact channel sums over the cropped image (integer, fixed order, no atomics), and from them on the device, in fp64,
+ * tables[frame][el] = trunc(clip((el - mean) * f + mean, 0, 255)), mean = (m0 * 0.114 + m1 * 0.587) + m2 * 0.299, m_c = sums[c] / (Hc * Wc):
+ * the reference's blue-green-red weights on the channels in stored order (randaugment.py:124).  No host synchronisation. */
+int alpro_augment_stats(const uint8_t* src, const int32_t* crop_offsets, const int32_t* ops, const double* args, uint64_t* sums,
+                        uint8_t* tables, int B, int T, int Hs, int Ws, int Hc, int Wc, void* stream);
+
 /* Round 5: the input of the fusion encoder as a gather of sequences (alpro_models.py:278-281, 325-330, 360-363: torch.cat of text and video
  * embeddings, with `text_embeds[neg_text]` / `video_embeds[neg_video]` for the hard negatives).  Sequence s of the (S, Lt + Lv, D) fusion batch
  * is text-pool sequence ti[s] followed by video-pool sequence vi[s]:
