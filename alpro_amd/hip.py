@@ -31,7 +31,7 @@ EXPORTS = ["alpro_hip_last_error", "alpro_hip_abi_version", "alpro_hip_set_optio
            "alpro_layernorm_bwd", "alpro_transpose", "alpro_transpose_batch", "alpro_gelu_bwd", "alpro_cls_mean_bwd", "alpro_scatter_add_rows", "alpro_gather_cast", "alpro_sumsq", "alpro_adamw_step", "alpro_gemm_tn_acc", "alpro_gemm_tn_acc_ws", "alpro_gemm_tn_workspace_bytes", "alpro_gemm_tn_ranges", "alpro_colsum_acc", "alpro_colsum_tn", "alpro_softmax_xent", "alpro_vtc_loss_fwd", "alpro_vtc_loss_bwd", "alpro_prepare_clips", "alpro_loss_scale_update", "alpro_add_layernorm_fwd", "alpro_layernorm_bwd_emit", "alpro_gemm_batch", "alpro_tproj_small", "alpro_attn_cls_fwd", "alpro_gemm_rows_f32", "alpro_gather_seq_fwd", "alpro_gather_seq_bwd", "alpro_scatter_add_rows_ordered",
            "alpro_hip_sched_workspace_bytes", "alpro_hip_set_sched_workspace", "alpro_hip_release_stream", "alpro_gemm_qkv_tattn", "alpro_add_layernorm_pre_mlp2", "alpro_adamw_step_lp",
            "alpro_gemm_rows_f32_relu_mask", "alpro_clip_pool", "alpro_adamw_step_groups", "alpro_attn_temporal_fwd_drop", "alpro_attn_temporal_bwd_drop",
-           "alpro_vit_final_pool_mode", "alpro_vit_final_pool_mode_bwd", "alpro_augment_stage", "alpro_augment_stats"]
+           "alpro_vit_final_pool_mode", "alpro_vit_final_pool_mode_bwd", "alpro_augment_stage", "alpro_augment_stats", "alpro_resized_crop"]
 
 
 class GemmDesc(ctypes.Structure):
@@ -60,6 +60,7 @@ class TransposeJob(ctypes.Structure):
 
 
 ADAMW_MAX_SEGMENTS = 32   # ALPRO_ADAMW_MAX_SEGMENTS
+RESAMPLE_MAX_TAPS = 257   # ALPRO_RESAMPLE_MAX_TAPS: the tap count of a 4096-pixel side resized to 64
 
 
 class AdamWSegment(ctypes.Structure):
@@ -154,6 +155,7 @@ def load():
     lib.alpro_prepare_clips.argtypes = [vp, i32, vp, f32, ctypes.POINTER(f32), ctypes.POINTER(f32), vp, vp, vp, i32, i32, i32, i32, vp]
     lib.alpro_augment_stage.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
     lib.alpro_augment_stats.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
+    lib.alpro_resized_crop.argtypes = [vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, vp]
     lib.alpro_vtc_loss_fwd.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
     lib.alpro_vtc_loss_bwd.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     if lib.alpro_hip_abi_version() != ABI_VERSION:
@@ -1175,4 +1177,59 @@ def augment_stage(src, ops, args, tables, dst=None, crop=None, out_hw=None):
     if tuple(dst.shape) != (B, T, 3, Hc, Wc) or not dst.is_contiguous():
         raise RuntimeError("augment_stage: dst must be a contiguous %s tensor, got shape %s" % ((B, T, 3, Hc, Wc), tuple(dst.shape)))
     _check(lib.alpro_augment_stage(_ptr(src), _ptr(dst), _ptr(crop), _ptr(ops), _ptr(args), _ptr(tables), B, T, Hs, Ws, Hc, Wc, _stream()), "alpro_augment_stage")
+    return dst
+
+
+def resized_crop(src, sizes, boxes, flips, S, dst=None, tmp=None):
+    """alpro_resized_crop: RandomResizedCrop + RandomHorizontalFlip of a batch of differently sized images, PIL's 8-bit bicubic
+    `crop().resize((S, S), BICUBIC)` bit for bit.  src: 1-D uint8 device buffer holding the (H, W, 3) interleaved images back to back
+    (input_gpu.pack_images); sizes: (H, W) per image; boxes: (top, left, h, w) per image; flips: truth value per image (None: no flips), all on
+    the HOST.  -> dst (B, 1, 3, S, S) uint8 planar.  tmp: at least B * max(h) * 3 * S bytes of uint8 device workspace (default: allocated).
+    The geometry and the fp64 coefficient tables (input_gpu.resample_table) go up in one host buffer and one copy; nothing synchronises."""
+    from alpro_amd.input_gpu import resample_ksize, resample_table
+    lib = load()
+    if not isinstance(src, torch.Tensor) or not src.is_cuda:
+        raise RuntimeError("resized_crop needs a device tensor, got %s (no CPU fallback)" % getattr(src, "device", type(src).__name__))
+    if src.dtype != torch.uint8:
+        raise RuntimeError("resized_crop needs uint8 pixels, got %s" % src.dtype)
+    if src.dim() != 1 or not src.is_contiguous():
+        raise RuntimeError("resized_crop needs the packed 1-D buffer of pack_images, got shape %s" % (tuple(src.shape),))
+    S, B = int(S), len(sizes)
+    if S < 4 or S % 4 != 0:
+        raise ValueError("resized_crop: output size %d is not a positive multiple of 4 (the vertical pass stores whole words)" % S)
+    flips = [False] * B if flips is None else list(flips)
+    if B < 1 or len(boxes) != B or len(flips) != B:
+        raise ValueError("resized_crop: %d sizes, %d boxes and %d flips for one batch" % (B, len(boxes), len(flips)))
+    need = 0
+    for b, ((H, W), (top, left, h, w)) in enumerate(zip(sizes, boxes)):
+        if H < 1 or W < 1:
+            raise ValueError("resized_crop: image %d has size %d x %d" % (b, H, W))
+        if h < 1 or w < 1:
+            raise ValueError("resized_crop: box (top %d, left %d, h %d, w %d) of image %d is empty: h and w must be >= 1" % (top, left, h, w, b))
+        if top < 0 or left < 0 or top + h > H or left + w > W:
+            raise ValueError("resized_crop: box (top %d, left %d, h %d, w %d) of image %d leaves its %d x %d image" % (top, left, h, w, b, H, W))
+        for extent in (h, w):
+            if resample_ksize(extent, S) > RESAMPLE_MAX_TAPS:
+                raise ValueError("resized_crop: %d pixels of image %d resized to %d need %d taps, above ALPRO_RESAMPLE_MAX_TAPS = %d"
+                                 % (extent, b, S, resample_ksize(extent, S), RESAMPLE_MAX_TAPS))
+        need += int(H) * int(W) * 3
+    if need > src.numel():
+        raise ValueError("resized_crop: the sizes add up to %d bytes, the packed buffer holds %d" % (need, src.numel()))
+    dev = src.device
+    if dst is None:
+        dst = torch.empty((B, 1, 3, S, S), dtype=torch.uint8, device=dev)
+    _dev(dst, torch.uint8)
+    if tuple(dst.shape) != (B, 1, 3, S, S) or not dst.is_contiguous():
+        raise RuntimeError("resized_crop: dst must be a contiguous %s tensor, got shape %s" % ((B, 1, 3, S, S), tuple(dst.shape)))
+    if dst.data_ptr() < src.data_ptr() + src.numel() and src.data_ptr() < dst.data_ptr() + dst.numel():
+        raise RuntimeError("resized_crop: dst (%d bytes at 0x%x) overlaps the source buffer (%d bytes at 0x%x)" % (dst.numel(), dst.data_ptr(), src.numel(), src.data_ptr()))
+    host, max_h, ktaps = resample_table(sizes, boxes, flips, S)
+    if tmp is None:
+        tmp = torch.empty(B * max_h * 3 * S, dtype=torch.uint8, device=dev)
+    _dev(tmp, torch.uint8)
+    if tmp.numel() < B * max_h * 3 * S or not tmp.is_contiguous():
+        raise RuntimeError("resized_crop: tmp must hold %d bytes (B %d x max h %d x 3 x S %d), got %d" % (B * max_h * 3 * S, B, max_h, S, tmp.numel()))
+    table = torch.from_numpy(host).to(dev)
+    meta, coef = table[:B * 64], table[B * 64:]
+    _check(lib.alpro_resized_crop(_ptr(src), src.numel(), _ptr(meta), _ptr(coef), _ptr(tmp), _ptr(dst), B, S, max_h, ktaps, _stream()), "alpro_resized_crop")
     return dst

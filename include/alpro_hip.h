@@ -311,6 +311,23 @@ int alpro_augment_stage(const uint8_t* src, uint8_t* dst, const int32_t* crop_of
 int alpro_augment_stats(const uint8_t* src, const int32_t* crop_offsets, const int32_t* ops, const double* args, uint64_t* sums,
                         uint8_t* tables, int B, int T, int Hs, int Ws, int Hc, int Wc, void* stream);
 
+/* RandomResizedCrop + RandomHorizontalFlip of the image-text stream (src/datasets/dataset_pretrain_sparse.py:125-193; still ABI 22: an
+ * addition): crop a box out of each of B differently sized images and resize it to S x S by PIL's 8-bit antialiased bicubic resampling
+ * (Image.crop().resize(BICUBIC)), bit for bit: a horizontal pass, the intermediate rounded to uint8, then a vertical pass, each
+ * out = clip8((2^21 + sum_t k[t] * pix[first + t]) >> 22) in 32-bit integers.  The coefficients are the CALLER's (fp64 on the host, PIL's order
+ * of operations: alpro_amd/input_gpu.py resample_coeffs); the kernels are integer only.
+ *   src: src_bytes bytes on the device, the images packed back to back, each (H, W, 3) uint8 interleaved.
+ *   meta (B, 8) int64 on the DEVICE: {byte offset in src, H, W, top, left, h, w, flip}; the box {top, left, h, w} must lie inside the image.
+ *   coef (B, 2, S, 2 + ktaps) int32 on the DEVICE: per image, axis (0 horizontal over w, 1 vertical over h) and output index {first tap
+ *   relative to the crop, tap count, k[0..ktaps)}, rows zero-padded to ktaps <= ALPRO_RESAMPLE_MAX_TAPS slots.
+ *   tmp: B * max_h * 3 * S bytes of workspace, max_h >= every h; dst (B, 1, 3, S, S) uint8 planar, column xx stored at S - 1 - xx where flip != 0.
+ * S % 4 == 0; tmp and dst 4-byte aligned; dst and tmp overlap neither src nor each other.  The kernels clamp every offset, size, box and tap
+ * index they read into its image, so no table content can move an access outside src or tmp.  No host synchronisation.
+ * ALPRO_RESAMPLE_MAX_TAPS is the tap count of a 4096-pixel side resized to 64 (2 * ceil(2 * 4096 / 64) + 1). */
+#define ALPRO_RESAMPLE_MAX_TAPS 257
+int alpro_resized_crop(const uint8_t* src, int64_t src_bytes, const int64_t* meta, const int32_t* coef, uint8_t* tmp, uint8_t* dst, int B, int S,
+                       int max_h, int ktaps, void* stream);
+
 /* Round 5: the input of the fusion encoder as a gather of sequences (alpro_models.py:278-281, 325-330, 360-363: torch.cat of text and video
  * embeddings, with `text_embeds[neg_text]` / `video_embeds[neg_video]` for the hard negatives).  Sequence s of the (S, Lt + Lv, D) fusion batch
  * is text-pool sequence ti[s] followed by video-pool sequence vi[s]:
