@@ -274,6 +274,17 @@ def torch_dtype(code):
 
 
 # ------------------------------------------------------------------------------------------------
+def _ld(t, n, what):
+    """Row stride, in elements, of a GEMM output or epilogue operand with n columns (ldc / ldr / ldc2 / ld_side of alpro_gemm_desc_t), after
+    _dev: stride(0) of a 2-D tensor -- a row-strided view keeps its buffer's row stride, as lda / ldw do -- and the last dimension of a
+    contiguous tensor of any other rank (its leading dimensions are taken flattened) or of a single row.  Fewer than n columns, or rows
+    that overlap, cannot be addressed through the descriptor and are refused."""
+    ld = t.stride(0) if t.dim() == 2 and t.shape[0] > 1 else t.shape[-1]
+    if t.dim() == 0 or t.shape[-1] < n or ld < t.shape[-1]:
+        raise RuntimeError("gemm: %s %s with strides %s cannot hold rows of %d columns" % (what, tuple(t.shape), tuple(t.stride()), n))
+    return ld
+
+
 def gemm(a, w, out=None, bias=None, act=ACT_NONE, out_dtype=None, alpha=1.0, row_scale=None, row_scale_group=1,
          residual=None, map_mode=MAP_IDENTITY, map_p0=0, map_p1=0, side=None, out_rows=None, pre_act=None, drop_p=0.0, drop_seed=0, bias2=None,
          c2_tiled=False, _desc_only=False):
@@ -293,7 +304,7 @@ def gemm(a, w, out=None, bias=None, act=ACT_NONE, out_dtype=None, alpha=1.0, row
     _dev(out, out_dtype)
     d = GemmDesc()
     d.A, d.W, d.C = a.data_ptr(), w.data_ptr(), out.data_ptr()
-    d.lda, d.ldw, d.ldc = a.stride(0), w.stride(0), out.shape[-1]
+    d.lda, d.ldw, d.ldc = a.stride(0), w.stride(0), _ld(out, N, "out")
     d.M, d.N, d.K = M, N, K
     d.dtype, d.c_dtype, d.alpha = _CODE[a.dtype], _CODE[out_dtype], alpha
     d.bias = _dev(bias, torch.float32).data_ptr() if bias is not None else None
@@ -301,12 +312,12 @@ def gemm(a, w, out=None, bias=None, act=ACT_NONE, out_dtype=None, alpha=1.0, row
     d.row_scale = _dev(row_scale, torch.float32).data_ptr() if row_scale is not None else None
     d.row_scale_group = row_scale_group
     d.residual = _dev(residual, torch.float32).data_ptr() if residual is not None else None
-    d.ldr = residual.shape[-1] if residual is not None else 0
+    d.ldr = _ld(residual, N, "residual") if residual is not None else 0
     d.map_mode, d.map_p0, d.map_p1 = map_mode, map_p0, map_p1
     d.side = _dev(side, torch.float32).data_ptr() if side is not None else None
-    d.ld_side = side.shape[-1] if side is not None else 0
+    d.ld_side = _ld(side, N, "side") if side is not None else 0
     d.C2 = _dev(pre_act, a.dtype).data_ptr() if pre_act is not None else None
-    d.ldc2 = pre_act.shape[-1] if pre_act is not None else 0
+    d.ldc2 = _ld(pre_act, 0 if c2_tiled else N, "pre_act") if pre_act is not None else 0
     d.c2_tiled = 1 if c2_tiled else 0
     if c2_tiled and not (pre_act is not None and pre_act.is_contiguous() and pre_act.numel() >= gemm_c2_tiled_rows(M, N, K, a.dtype) * N > 0):
         raise RuntimeError("gemm: c2_tiled needs a contiguous pre_act buffer of gemm_c2_tiled_rows(M, N, K, dtype) x N elements (0 rows = not offered for this shape)")

@@ -486,7 +486,11 @@ int alpro_scatter_add_rows_ordered(const float* src, const int64_t* idx, float* 
  * B = X row-major in a 16-bit dtype, contraction over tokens split across the grid (gemm_tn.hip).  C must be
  * initialised (zero or the running gradient).  fp32 operands: use alpro_transpose + alpro_gemm.
  * colsum (optional, (N) fp32, atomically accumulated): colsum[n] += sum_m A[m, n] -- the bias gradient of the same Linear,
- * taken from the dY fragments the kernel already holds (nn.Linear backward: grad_bias = grad_output.sum(0)). */
+ * taken from the dY fragments the kernel already holds (nn.Linear backward: grad_bias = grad_output.sum(0)).
+ * Input contract: lda, ldb multiples of 8 covering N, K rounded up to 8 -- rows are read in whole 16-byte chunks, so the columns between
+ * N (K) and the next multiple of 8 must be readable memory; their CONTENTS are free (NaN included: they only reach rows / columns of the
+ * tile that are never stored), and so is everything in rows at and beyond M (never read: a zero page stands in).
+ * tests/test_hip_gemm_exact.py runs with NaN in all of them. */
 int alpro_gemm_tn_acc(const void* A, int64_t lda, const void* B, int64_t ldb, float* C, int64_t ldc, int dtype, int M,
                       int N, int K, float* colsum, void* stream);
 
