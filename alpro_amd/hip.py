@@ -31,7 +31,8 @@ EXPORTS = ["alpro_hip_last_error", "alpro_hip_abi_version", "alpro_hip_set_optio
            "alpro_layernorm_bwd", "alpro_transpose", "alpro_transpose_batch", "alpro_gelu_bwd", "alpro_cls_mean_bwd", "alpro_scatter_add_rows", "alpro_gather_cast", "alpro_sumsq", "alpro_adamw_step", "alpro_gemm_tn_acc", "alpro_gemm_tn_acc_ws", "alpro_gemm_tn_workspace_bytes", "alpro_gemm_tn_ranges", "alpro_colsum_acc", "alpro_colsum_tn", "alpro_softmax_xent", "alpro_vtc_loss_fwd", "alpro_vtc_loss_bwd", "alpro_prepare_clips", "alpro_loss_scale_update", "alpro_add_layernorm_fwd", "alpro_layernorm_bwd_emit", "alpro_gemm_batch", "alpro_tproj_small", "alpro_attn_cls_fwd", "alpro_gemm_rows_f32", "alpro_gather_seq_fwd", "alpro_gather_seq_bwd", "alpro_scatter_add_rows_ordered",
            "alpro_hip_sched_workspace_bytes", "alpro_hip_set_sched_workspace", "alpro_hip_release_stream", "alpro_gemm_qkv_tattn", "alpro_add_layernorm_pre_mlp2", "alpro_adamw_step_lp",
            "alpro_gemm_rows_f32_relu_mask", "alpro_clip_pool", "alpro_adamw_step_groups", "alpro_attn_temporal_fwd_drop", "alpro_attn_temporal_bwd_drop",
-           "alpro_vit_final_pool_mode", "alpro_vit_final_pool_mode_bwd", "alpro_augment_stage", "alpro_augment_stats", "alpro_resized_crop"]
+           "alpro_vit_final_pool_mode", "alpro_vit_final_pool_mode_bwd", "alpro_augment_stage", "alpro_augment_stats", "alpro_resized_crop",
+           "alpro_sim_topk", "alpro_sim_topk_workspace_bytes"]
 
 
 class GemmDesc(ctypes.Structure):
@@ -158,6 +159,9 @@ def load():
     lib.alpro_resized_crop.argtypes = [vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, vp]
     lib.alpro_vtc_loss_fwd.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
     lib.alpro_vtc_loss_bwd.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.alpro_sim_topk_workspace_bytes.argtypes = [i32, i32, i32, i32]
+    lib.alpro_sim_topk_workspace_bytes.restype = ctypes.c_size_t
+    lib.alpro_sim_topk.argtypes = [vp, i32, vp, i32, i32, i32, f32, i32, vp, vp, vp, ctypes.c_size_t, vp]
     if lib.alpro_hip_abi_version() != ABI_VERSION:
         raise RuntimeError("libalpro_hip.so ABI version mismatch")
     _lib = lib
@@ -741,6 +745,32 @@ def clip_pool(logits, C, mode="mean"):
     _check(lib.alpro_clip_pool(_ptr(logits), logits.stride(0), _ptr(pooled), pooled.stride(0), _ptr(pred), B, C, A, POOL_MODES[mode], _stream()),
            "alpro_clip_pool")
     return pooled, pred
+
+
+TOPK_MAX_K = 128   # ALPRO_TOPK_MAX_K
+
+
+def sim_topk(q, g, k, scale=1.0, chunk=0):
+    """Similarity + top-k without the (nq, ng) matrix (alpro_sim_topk): q (nq, 256), g (ng, 256) fp32 contiguous -> (values (nq, k) fp32 =
+    q[i] . g[j] * scale, indices (nq, k) int32), each row the k best gallery rows by (value descending, index ascending); ng < k leaves
+    -inf / -1 at the tail.  chunk: gallery rows per partial pass (0 = the library's choice; the result does not depend on it)."""
+    lib = load()
+    for name, t in (("q", q), ("g", g)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError("sim_topk: %s must be a device tensor (got %s): the hot path has no CPU fallback" % (name, getattr(t, "device", type(t))))
+        if t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous():
+            raise RuntimeError("sim_topk: %s must be a contiguous 2-D fp32 tensor (got %s %s, strides %s)" % (name, t.dtype, tuple(t.shape), tuple(t.stride())))
+    if q.shape[1] != g.shape[1] or q.device != g.device:
+        raise RuntimeError("sim_topk: q %s and g %s must share the feature width and the device" % (tuple(q.shape), tuple(g.shape)))
+    nq, ng, d, k, chunk = q.shape[0], g.shape[0], q.shape[1], int(k), int(chunk)
+    need = int(lib.alpro_sim_topk_workspace_bytes(nq, ng, k, chunk))
+    if need == 0:
+        raise RuntimeError("alpro_sim_topk_workspace_bytes refused the arguments: %s" % lib.alpro_hip_last_error().decode())
+    ws = torch.empty(need, dtype=torch.uint8, device=q.device)   # (the caching allocator hands out 512-byte aligned blocks)
+    val = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+    idx = torch.empty((nq, k), dtype=torch.int32, device=q.device)
+    _check(lib.alpro_sim_topk(_ptr(q), nq, _ptr(g), ng, d, k, float(scale), chunk, _ptr(val), _ptr(idx), _ptr(ws), need, _stream()), "alpro_sim_topk")
+    return val, idx
 
 
 def patchify(img, dtype):

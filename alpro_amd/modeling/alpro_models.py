@@ -525,6 +525,25 @@ class AlproForVideoTextRetrieval(AlproBaseModel):
         out = self._fusion(torch.cat([text_embeds, ve], dim=1), torch.cat([text_input_mask, video_atts], dim=1))
         return dict(logits=_linear32(out[:, 0, :], self.itm_head), itc_scores=video_feat @ text_feat.t() / self.temp)
 
+    @torch.no_grad()
+    def score_pair_list(self, video_embeds, text_embeds, text_input_mask, vi, ci):
+        """ITM logits (S, 2) fp32 of S listed (video, caption) pairs over cached encoder outputs -- stage 2 of the two-stage search
+        (alpro_amd/retrieval_eval.py rerank_retrieval): sequence s = [text_embeds[ci[s]] ; video_embeds[vi[s]]] (vi, ci (S,) int64 on the device),
+        gathered by alpro_gather_seq_fwd (BertModel.forward encoder_embeds_parts), never repeated or concatenated; the last fusion layer's row-wise
+        tail runs on the S [CLS] rows alone, as in AlproForSequenceClassification.answer_logits (ALPRO_FUSION_TAIL_ROWS=0: every row).  Evaluation
+        only: the model must be in eval mode (no dropout, no RNG draw)."""
+        if self.training:
+            raise RuntimeError("score_pair_list scores cached features for evaluation: call model.eval() first")
+        S, Lt = vi.numel(), text_embeds.shape[1]
+        L = Lt + video_embeds.shape[1]
+        att = torch.ones((S, L), dtype=text_input_mask.dtype, device=text_input_mask.device)
+        att[:, :Lt] = text_input_mask[ci]
+        tail = os.environ.get("ALPRO_FUSION_TAIL_ROWS", "1") != "0" and text_embeds.is_cuda
+        rows = torch.arange(S, device=vi.device, dtype=torch.long) * L if tail else None
+        out = self.text_encoder.bert(encoder_embeds_parts=(text_embeds, video_embeds, ci, vi), attention_mask=att, return_dict=True, mode='fusion',
+                                     out_rows=rows).last_hidden_state
+        return _linear32(out if rows is not None else out[:, 0, :], self.itm_head).float()
+
 
 _HEAD_ROW_CHUNK = 512   # alpro_gemm_rows_f32 is sized for a handful of rows (_rows_ok): multi-clip evaluation's B * C rows run in chunks of this many
 

@@ -4,6 +4,9 @@ Same result records and metrics as the reference's `inference_retrieval` / `eval
 (src/tasks/run_video_retrieval.py:515-690), but every video goes through the visual encoder once and every caption through the
 text encoder once; only the fusion pass + ITM head runs per (video, caption) pair, in mini-batches.  For V videos x C captions
 with mini-batches of b captions the reference runs the ViT V*ceil(C/b) times and the text encoder on V*C captions.
+
+Beside the reference's all-pairs evaluation: a two-stage search over the same cached features (rerank_retrieval / rerank_metrics: the k best
+candidates per query by the contrastive features through hip.sim_topk, fusion + ITM on those only), for galleries where V*C passes are too many.
 """
 import math
 from collections import defaultdict
@@ -73,6 +76,95 @@ def score_all_pairs(model, videos, text_input_ids, text_input_mask, pair_bsz=512
         from alpro_amd.modeling.alpro_models import _linear32
         score[s:s + idx.numel()] = torch.softmax(_linear32(out[:, 0, :], model.itm_head).float(), dim=1)[:, 1]
     return score.view(V, C), sim
+
+
+@torch.no_grad()
+def encode_gallery(model, videos, bsz=8):
+    """Every video through the visual encoder once, `bsz` at a time: videos (V, T, C, H, W) or an iterable of (1, T, C, H, W) clips ->
+    (video_embeds (V, 1+N, D), video_feat (V, 256)), device tensors."""
+    model.eval()
+    clips = videos if torch.is_tensor(videos) else torch.cat(list(videos), 0)
+    ve, vf = [], []
+    for i in range(0, clips.shape[0], bsz):
+        e, f = model.encode_video(clips[i:i + bsz])
+        ve.append(e)
+        vf.append(f)
+    return torch.cat(ve, 0), torch.cat(vf, 0)
+
+
+@torch.no_grad()
+def encode_captions(model, ids, mask, bsz=1024):
+    """Every caption through the text encoder once, `bsz` at a time: ids, mask (C, Lt) -> (text_embeds (C, Lt, D), text_feat (C, 256))."""
+    model.eval()
+    te, tf = [], []
+    for i in range(0, ids.shape[0], bsz):
+        e, f = model.encode_text(ids[i:i + bsz], mask[i:i + bsz])
+        te.append(e)
+        tf.append(f)
+    return torch.cat(te, 0), torch.cat(tf, 0)
+
+
+@torch.no_grad()
+def rerank_retrieval(model, video_embeds, video_feat, text_embeds, text_feat, text_input_mask, k, pair_bsz=512):
+    """Two-stage search over cached features (the k_test evaluation of ALBEF / BLIP; the reference itself scores every pair, which
+    score_all_pairs reproduces).  Stage 1: the k best videos per caption and the k best captions per video by the 256-d contrastive
+    features (hip.sim_topk, scale = 1 / temp: no (V, C) matrix).  Stage 2: only the union of the two candidate sets goes through the
+    fusion encoder and the ITM head (model.score_pair_list), every pair once, in the order of vi * C + ci, `pair_bsz` pairs at a time --
+    at most 2 k max(V, C) fusion passes instead of V * C.  One host read (the pair count) and the read of `temp`.
+    Returns a dict of device tensors: t2v_idx (C, k) int32 video indices, t2v_sim (C, k) similarity / temp, t2v_score (C, k)
+    softmax(itm logits)[:, 1]; v2t_idx / v2t_sim / v2t_score (V, k) likewise with caption indices.  Where k exceeds the gallery the tail
+    of a row is idx -1, sim -inf, score -inf."""
+    from alpro_amd import hip
+    model.eval()
+    V, C = video_feat.shape[0], text_feat.shape[0]
+    vf, tf = video_feat.float().contiguous(), text_feat.float().contiguous()
+    scale = 1.0 / float(model.temp)
+    t2v_sim, t2v_idx = hip.sim_topk(tf, vf, k, scale=scale)
+    v2t_sim, v2t_idx = hip.sim_topk(vf, tf, k, scale=scale)
+    dev = vf.device
+    t2v_pair = t2v_idx.long() * C + torch.arange(C, device=dev)[:, None]          # pair id = vi * C + ci
+    v2t_pair = torch.arange(V, device=dev)[:, None] * C + v2t_idx.long()
+    t2v_ok, v2t_ok = t2v_idx >= 0, v2t_idx >= 0
+    pairs = torch.unique(torch.cat([t2v_pair[t2v_ok], v2t_pair[v2t_ok]]))        # sorted; its length is the one host read
+    score = torch.empty(pairs.numel(), dtype=torch.float32, device=dev)
+    for s in range(0, pairs.numel(), pair_bsz):
+        p = pairs[s:s + pair_bsz]
+        logits = model.score_pair_list(video_embeds, text_embeds, text_input_mask, torch.div(p, C, rounding_mode="floor"), p % C)
+        score[s:s + p.numel()] = torch.softmax(logits, dim=1)[:, 1]
+    ninf = torch.full((), float("-inf"), dtype=torch.float32, device=dev)
+
+    def lookup(pair, ok):
+        pos = torch.searchsorted(pairs, pair.clamp(min=0).reshape(-1)).clamp(max=max(pairs.numel() - 1, 0)).view(pair.shape)
+        return torch.where(ok, score[pos], ninf)
+
+    return dict(t2v_idx=t2v_idx, t2v_sim=t2v_sim, t2v_score=lookup(t2v_pair, t2v_ok),
+                v2t_idx=v2t_idx, v2t_sim=v2t_sim, v2t_score=lookup(v2t_pair, v2t_ok))
+
+
+@torch.no_grad()
+def rerank_metrics(idx, score, sim, gt):
+    """R@1/5/10, median and mean rank of a re-ranked search: idx / score / sim (Q, k) are each query's candidates (idx -1 = no candidate), gt (Q,)
+    its ground-truth gallery index.  A query's final order is its candidates sorted by (score descending, sim descending, idx ascending);
+    with every column as a candidate and a constant sim that is the stable descending sort of the reference's eval_retrieval
+    (run_video_retrieval.py:541-555).  `outside` counts the queries whose ground truth is not among their candidates; such a query counts as
+    rank k + 1 in medianR and meanR, which are therefore LOWER BOUNDS when outside > 0.  R@1/5/10 are exact for k >= 10 (an outside query
+    ranks below every candidate), which is why a smaller k raises ValueError."""
+    idx, score, sim = torch.as_tensor(idx), torch.as_tensor(score), torch.as_tensor(sim)
+    Q, k = idx.shape
+    if k < 10:
+        raise ValueError("rerank_metrics: k=%d candidates per query, need >= 10 for an exact R@10" % k)
+    gt = torch.as_tensor(gt).to(idx.device).view(-1, 1).to(idx.dtype)
+    hit = idx == gt
+    inside = hit.any(1)
+    neg = torch.full((), float("-inf"), dtype=score.dtype, device=score.device)
+    gs = torch.where(hit, score, neg).max(1, keepdim=True)[0]     # the ground truth's own score / sim (idx holds it at most once)
+    gm = torch.where(hit, sim, neg.to(sim.dtype)).max(1, keepdim=True)[0]
+    before = (idx >= 0) & ((score > gs) | ((score == gs) & ((sim > gm) | ((sim == gm) & (idx < gt)))))
+    rank = torch.where(inside, 1 + before.sum(1), torch.full_like(inside, k + 1, dtype=torch.long))
+    r = rank.cpu().numpy()
+    ins = inside.cpu().numpy()
+    return dict(r1=100 * int((ins & (r <= 1)).sum()) / Q, r5=100 * int((ins & (r <= 5)).sum()) / Q, r10=100 * int((ins & (r <= 10)).sum()) / Q,
+                medianR=float(np.median(r)), meanR=float(np.mean(r)), outside=int(Q - ins.sum()))
 
 
 def records_from_matrices(score, sim, vid_ids, txt_ids):

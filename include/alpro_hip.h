@@ -594,6 +594,22 @@ int alpro_adamw_step_groups(float* p, float* g, float* m, float* v, int64_t n, c
 int alpro_loss_scale_update(float* dyn_state, const float* gnorm_sq, float growth, float backoff, int window, float min_scale,
                             float max_scale, void* stream);
 
+/* ---- similarity + top-k without the matrix (stage 1 of the two-stage retrieval search; ALBEF / BLIP k_test.  The reference's evaluation,
+ * run_video_retrieval.py:642-690, scores every pair; alpro_amd/retrieval_eval.py rerank_retrieval is this repo's addition) ----
+ * q (nq, d) and g (ng, d): fp32, row-major, contiguous, 16-byte aligned; d must be 256 (the model's embed_dim).  s[i][j] = the fp32 fmaf chain
+ * over k = 0..255 in k order from 0 (v_mfma_f32_32x32x2_f32), -0.0 canonicalised to +0.0.  Row i of out_val / out_idx (nq, k), 1 <= k <=
+ * ALPRO_TOPK_MAX_K: the k largest s[i][:] by (value descending, gallery index ascending) -- a total order, so the result is unique and does
+ * not depend on `chunk`, the grid or the CUs available -- out_val = s * scale (one fp32 multiply).  ng < k: the tail is idx -1 / val -inf.
+ * Inputs are assumed finite (a NaN gets some place in the order, nothing faults).
+ * chunk: gallery rows per partial pass; 0 = the library's choice (a function of nq and ng alone), any positive multiple of 32 is taken as given.
+ * workspace: 256-byte aligned, at least alpro_sim_topk_workspace_bytes(nq, ng, k, chunk) bytes (0 = the arguments are refused, text in
+ * alpro_hip_last_error); phase 1 writes min(k, chunk) 64-bit keys per (query, chunk) there, phase 2 merges them per query.  Every argument is
+ * checked before the first HIP call.  No atomics: bitwise reproducible. */
+#define ALPRO_TOPK_MAX_K 128
+size_t alpro_sim_topk_workspace_bytes(int nq, int ng, int k, int chunk);
+int alpro_sim_topk(const float* q, int nq, const float* g, int ng, int d, int k, float scale, int chunk, float* out_val, int32_t* out_idx,
+                   void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
