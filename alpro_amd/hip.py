@@ -32,7 +32,7 @@ EXPORTS = ["alpro_hip_last_error", "alpro_hip_abi_version", "alpro_hip_set_optio
            "alpro_hip_sched_workspace_bytes", "alpro_hip_set_sched_workspace", "alpro_hip_release_stream", "alpro_gemm_qkv_tattn", "alpro_add_layernorm_pre_mlp2", "alpro_adamw_step_lp",
            "alpro_gemm_rows_f32_relu_mask", "alpro_clip_pool", "alpro_adamw_step_groups", "alpro_attn_temporal_fwd_drop", "alpro_attn_temporal_bwd_drop",
            "alpro_vit_final_pool_mode", "alpro_vit_final_pool_mode_bwd", "alpro_augment_stage", "alpro_augment_stats", "alpro_resized_crop",
-           "alpro_sim_topk", "alpro_sim_topk_workspace_bytes"]
+           "alpro_sim_topk", "alpro_sim_topk_workspace_bytes", "alpro_attn_probs"]
 
 
 class GemmDesc(ctypes.Structure):
@@ -162,6 +162,7 @@ def load():
     lib.alpro_sim_topk_workspace_bytes.argtypes = [i32, i32, i32, i32]
     lib.alpro_sim_topk_workspace_bytes.restype = ctypes.c_size_t
     lib.alpro_sim_topk.argtypes = [vp, i32, vp, i32, i32, i32, f32, i32, vp, vp, vp, ctypes.c_size_t, vp]
+    lib.alpro_attn_probs.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, i32, i32, i32, vp]
     if lib.alpro_hip_abi_version() != ABI_VERSION:
         raise RuntimeError("libalpro_hip.so ABI version mismatch")
     _lib = lib
@@ -642,6 +643,39 @@ def attn(qkv, batch, L, H, scale, key_bias=None, want_lse=False, drop_p=0.0, dro
                               _ptr(cls_q), cls_group, _ptr(cls_out), _stream()), "alpro_attn_fwd")
     res = (out,) + ((lse,) if want_lse else ()) + ((cls_out,) if cls_q is not None else ())
     return res if len(res) > 1 else out
+
+
+def _window(r, L):
+    """(start, stop) of a Python-style range over 0..L (None: all of it) -> (start, count)."""
+    if r is None:
+        return 0, L
+    lo, hi = int(r[0]), int(r[1])
+    return lo, hi - lo
+
+
+def attn_probs(qkv, lse, batch, L, H, scale, key_bias=None, q_range=None, k_range=None):
+    """The softmax probabilities attn() never materialises (alpro_attn_probs): qkv (batch*L, 3*H*64) as the qkv GEMM wrote it, lse (batch, H, L)
+    fp32 from attn(..., want_lse=True) on the same qkv / scale / key_bias -> (batch, H, nq, nk) fp32, the window q_range = (q_start, q_stop),
+    k_range = (k_start, k_stop) of every (L, L) map (None: all rows / all keys).  Normalised over all L keys (a window is a slice, not a
+    renormalised map); the probabilities before dropout."""
+    for name, t in (("qkv", qkv), ("lse", lse)) + ((("key_bias", key_bias),) if key_bias is not None else ()):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError("attn_probs: %s must be a device tensor (got %s): the hot path has no CPU fallback" % (name, getattr(t, "device", type(t))))
+    lib = load()
+    batch, L, H = int(batch), int(L), int(H)
+    if qkv.dtype not in _CODE or qkv.dim() != 2 or tuple(qkv.shape) != (batch * L, 3 * H * 64) or not qkv.is_contiguous():
+        raise RuntimeError("attn_probs: qkv must be a contiguous (batch*L, 3*H*64) = (%d, %d) fp32 / bf16 / fp16 tensor (got %s %s, strides %s)"
+                           % (batch * L, 3 * H * 64, qkv.dtype, tuple(qkv.shape), tuple(qkv.stride())))
+    if lse.dtype != torch.float32 or tuple(lse.shape) != (batch, H, L) or not lse.is_contiguous():
+        raise RuntimeError("attn_probs: lse must be a contiguous (batch, H, L) = (%d, %d, %d) fp32 tensor (got %s %s)" % (batch, H, L, lse.dtype, tuple(lse.shape)))
+    if key_bias is not None and (key_bias.dtype != torch.float32 or tuple(key_bias.shape) != (batch, L) or not key_bias.is_contiguous()):
+        raise RuntimeError("attn_probs: key_bias must be a contiguous (batch, L) = (%d, %d) fp32 tensor (got %s %s)" % (batch, L, key_bias.dtype, tuple(key_bias.shape)))
+    (q0, nq), (k0, nk) = _window(q_range, L), _window(k_range, L)
+    # (the library refuses a window outside 0..L or an empty one; max(.., 0): such a call never allocates a negative size)
+    out = torch.empty((batch, H, max(nq, 0), max(nk, 0)), dtype=torch.float32, device=qkv.device)
+    _check(lib.alpro_attn_probs(_ptr(qkv), _ptr(lse), _ptr(key_bias), _ptr(out), _CODE[qkv.dtype], batch, L, H, float(scale), q0, nq, k0, nk, _stream()),
+           "alpro_attn_probs")
+    return out
 
 
 def qkv_tattn_ok(a, T):

@@ -145,17 +145,18 @@ class BertLayer(nn.Module):
         o32_c = hip.layernorm(s2_c, self.output.LayerNorm.weight, self.output.LayerNorm.bias, eps, f32)
         return s1_c, a32_c, s2_c, o32_c
 
-    def forward(self, h32, h_t, key_bias, B, L, rows=None):
+    def forward(self, h32, h_t, key_bias, B, L, rows=None, tap=None):
         """h32 (B*L, H) fp32 residual stream, h_t the same in the operand dtype; returns the next pair (of the `rows` only, if given)."""
-        o32, o_t, _ = self.forward_train(h32, h_t, key_bias, B, L, save=False, rows=rows)
+        o32, o_t, _ = self.forward_train(h32, h_t, key_bias, B, L, save=False, rows=rows, tap=tap)
         return o32, o_t
 
     # ---- training path ---------------------------------------------------------------------------------
-    def forward_train(self, h32, h_t, key_bias, B, L, save=True, rows=None):
+    def forward_train(self, h32, h_t, key_bias, B, L, save=True, rows=None, tap=None):
         """rows (optional, LongTensor of flat row indices): the only rows of this layer's OUTPUT anybody reads (the last fusion layer: [CLS] rows, the
         MLM pairs' text rows, the positives' patch rows -- a quarter of the 4B x 237).  Attention still runs over every row (all keys / values are
         needed, and the kernel's unit is a whole sequence); everything behind it -- attention-output dense, both LayerNorms, the FFN -- is row-wise
-        and runs on the gathered rows only; the outputs are then (len(rows), D)."""
+        and runs on the gathered rows only; the outputs are then (len(rows), D).
+        tap (optional, _AttnTap): output_attentions -- receives this layer's softmax probabilities, one more launch on its own qkv / lse / key bias."""
         hp, seed1, seed2, ap, seed_a = self._drop()
         dt = rt.compute_dtype()
         sa, so = self.attention.self, self.attention.output
@@ -171,6 +172,8 @@ class BertLayer(nn.Module):
             ctx, lse, ctx_c = hip.attn(qkv, B, L, H, scale, key_bias, want_lse=True, drop_p=ap, drop_seed=seed_a, cls_q=self._cls_qkv(hc), cls_group=1)
         else:
             ctx, lse = hip.attn(qkv, B, L, H, scale, key_bias, want_lse=True, drop_p=ap, drop_seed=seed_a)
+        if tap is not None:   # the probabilities before dropout (xbert.py:323,343); with precise [CLS] rows the [CLS] query row is the 16-bit graph's
+            tap.add(qkv, lse, B, L, H, scale, key_bias)
         ctx_full, M_full = ctx, h_t.shape[0]
         if rows is not None and cp:
             raise RuntimeError("BertLayer: an output row subset is supported on the fusion layers only")
@@ -256,6 +259,18 @@ class BertLayer(nn.Module):
         wT = (None, tr.transposed_operand(self._ops, "qkv_w^T", (sa.query.weight, sa.key.weight, sa.value.weight), dt))
         dh_t = tr.dgrad(dqkv, wT[1])
         return ds1, dh_t
+
+
+class _AttnTap:
+    """Collects the attention probabilities of the layers of one pass (BertModel.forward output_attentions): (B, H, L, L) fp32 per layer, or the
+    window (q_range, k_range) of every map only -- hip.attn_probs never forms the rest."""
+
+    def __init__(self, window=None):
+        self.q_range, self.k_range = window if window is not None else (None, None)
+        self.maps = []
+
+    def add(self, qkv, lse, B, L, H, scale, key_bias):
+        self.maps.append(hip.attn_probs(qkv, lse, B, L, H, scale, key_bias, q_range=self.q_range, k_range=self.k_range))
 
 
 class BertEncoder(nn.Module):
@@ -388,14 +403,40 @@ class BertModel(BertPreTrainedModel):
         """(B, L) {0,1} -> additive fp32 bias (1 - m) * -10000 (xbert.py:936-937)."""
         return ((1.0 - attention_mask.to(torch.float32)) * -10000.0).contiguous()
 
-    def forward(self, input_ids=None, attention_mask=None, encoder_embeds=None, return_dict=True, mode='multi_modal', encoder_embeds_parts=None, out_rows=None, **unused):
-        """encoder_embeds_parts (this repo's extension; the reference passes encoder_embeds): (text_pool (Pt, Lt, D), video_pool (Pv, Lv, D), ti (S,),
+    def output_flags(self, output_attentions=None, output_hidden_states=None):
+        """(output_attentions, output_hidden_states) as forward resolves them: None takes the config's value (xbert.py:977-980)."""
+        oa = output_attentions if output_attentions is not None else _cfg_get(self.config, "output_attentions", False)
+        oh = output_hidden_states if output_hidden_states is not None else _cfg_get(self.config, "output_hidden_states", False)
+        return bool(oa), bool(oh)
+
+    @staticmethod
+    def _result(out, hidden_states, attentions, return_dict):
+        if not return_dict:
+            if hidden_states is None and attentions is None:
+                return (out,)
+            # xbert.py:1072 + :613-623: (sequence_output, pooled_output) + the encoder's (hidden_states, attentions) that are not None
+            return (out, None) + tuple(v for v in (hidden_states, attentions) if v is not None)
+        return SimpleNamespace(last_hidden_state=out, pooler_output=None, hidden_states=hidden_states, attentions=attentions,
+                               past_key_values=None, cross_attentions=None)
+
+    def forward(self, input_ids=None, attention_mask=None, encoder_embeds=None, return_dict=True, mode='multi_modal', encoder_embeds_parts=None, out_rows=None,
+                output_attentions=None, output_hidden_states=None, attn_window=None, **unused):
+        """output_attentions / output_hidden_states (xbert.py:953-954, None: the config's value): `attentions` = one (B, H, L, L) fp32 tensor per
+        layer run, the softmax BEFORE dropout (hip.attn_probs on the layer's own qkv / lse / key bias); `hidden_states` = every layer's input
+        and the final output, (B, L, D) fp32 ((len(out_rows), D) for the last one under out_rows).  Both are detached copies -- unlike the
+        reference's they carry no autograd graph -- and asking for them changes no other result, gradient or dropout draw.
+        attn_window (this repo's extension): ((q_start, q_stop), (k_start, k_stop)) -- each `attentions` entry is that window of the map only,
+        (B, H, nq, nk); the rest is never computed (alpro_amd.grounding).
+        encoder_embeds_parts (this repo's extension; the reference passes encoder_embeds): (text_pool (Pt, Lt, D), video_pool (Pv, Lv, D), ti (S,),
         vi (S,)) -- the fusion batch as a gather, sequence s = [text_pool[ti[s]] ; video_pool[vi[s]]], i.e. what the reference's
         torch.cat([text_embeds, video_embeds], dim=1) over concatenated / index-selected batches holds (alpro_models.py:278-281,325-330,360-363),
         built by one kernel and differentiated by one (alpro_gather_seq_fwd / _bwd) instead of materialised by torch.cat and autograd.
         out_rows (this repo's extension): flat indices into the (B * L) output rows -- last_hidden_state is then (len(out_rows), D), those rows only, and
         the last layer's row-wise tail runs on them alone (BertLayer.forward_train)."""
         parts = encoder_embeds_parts
+        want_att, want_hid = self.output_flags(output_attentions, output_hidden_states)
+        tap = _AttnTap(attn_window) if want_att else None       # (both None with the flags off: no launch, no allocation)
+        hidden = [] if want_hid else None
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             lo, hi = self.encoder.layer_range(mode)
             params = [p for i in range(lo, hi) for p in self.encoder.layer[i].parameters()]
@@ -403,15 +444,13 @@ class BertModel(BertPreTrainedModel):
                 params += list(self.embeddings.parameters())
             run = _BertRun(self, input_ids, attention_mask, mode)
             run.out_rows = out_rows
+            run.tap, run.hidden = tap, hidden
             if parts is not None:
                 run.parts = (parts[2].contiguous(), parts[3].contiguous())
                 out = tr.run_anchored(run, [parts[0], parts[1]], params)
             else:
                 out = tr.run_anchored(run, [encoder_embeds] if encoder_embeds is not None else [], params)
-            if not return_dict:
-                return (out,)
-            return SimpleNamespace(last_hidden_state=out, pooler_output=None, hidden_states=None, attentions=None,
-                                   past_key_values=None, cross_attentions=None)
+            return self._result(out, tuple(hidden) if want_hid else None, tuple(tap.maps) if want_att else None, return_dict)
         dt = rt.compute_dtype()
         cfg = self.config
         if parts is not None:
@@ -435,12 +474,20 @@ class BertModel(BertPreTrainedModel):
         kb = self.key_bias(attention_mask)
         lo, hi = self.encoder.layer_range(mode)
         for i in range(lo, hi):
-            h32, h_t = self.encoder.layer[i](h32, h_t, kb, B, L, rows=out_rows if i == hi - 1 else None)
+            if want_hid:
+                hidden.append(_hidden_copy(h32, B, L))
+            h32, h_t = self.encoder.layer[i](h32, h_t, kb, B, L, rows=out_rows if i == hi - 1 else None, tap=tap)
         out = h32.view(B, L, -1) if out_rows is None else h32
-        if not return_dict:
-            return (out,)
-        return SimpleNamespace(last_hidden_state=out, pooler_output=None, hidden_states=None, attentions=None,
-                               past_key_values=None, cross_attentions=None)
+        if want_hid:
+            hidden.append(_hidden_copy(h32, B, L, out_rows))
+        return self._result(out, tuple(hidden) if want_hid else None, tuple(tap.maps) if want_att else None, return_dict)
+
+
+def _hidden_copy(h32, B, L, out_rows=None):
+    """One `hidden_states` entry: a detached COPY of the fp32 residual stream -- the stream's first tensor may be the caller's encoder_embeds, its
+    last one is last_hidden_state, and a precise-[CLS] layer rewrites rows of its own output in place; a copy is none of these."""
+    h = h32.detach().clone()
+    return h.view(B, L, -1) if out_rows is None else h
 
 
 class _BertRun:
@@ -450,6 +497,7 @@ class _BertRun:
         self.m, self.ids, self.mask, self.mode = model, input_ids, attention_mask, mode
         self.parts = None   # (ti, vi): the input is a gather of (text pool, video pool) sequences, the two activations of forward()
         self.out_rows = None   # flat indices of the only output rows the caller reads (BertModel.forward out_rows)
+        self.tap = self.hidden = None   # output_attentions / output_hidden_states: the collectors BertModel.forward reads after the pass
 
     def forward(self, encoder_embeds=None, video_pool=None):
         m, cfg = self.m, self.m.config
@@ -493,11 +541,15 @@ class _BertRun:
         self.prefix = k > 0
         for i in range(lo, hi):
             rows = self.out_rows if i == hi - 1 else None
+            if self.hidden is not None:
+                self.hidden.append(_hidden_copy(h32, B, L))
             if i < first:
-                h32, h_t = m.encoder.layer[i](h32, h_t, kb, B, L, rows=rows)
+                h32, h_t = m.encoder.layer[i](h32, h_t, kb, B, L, rows=rows, tap=self.tap)
                 continue
-            h32, h_t, sv = m.encoder.layer[i].forward_train(h32, h_t, kb, B, L, rows=rows)
+            h32, h_t, sv = m.encoder.layer[i].forward_train(h32, h_t, kb, B, L, rows=rows, tap=self.tap)
             self.saved.append(sv)
+        if self.hidden is not None:
+            self.hidden.append(_hidden_copy(h32, B, L, self.out_rows))
         return h32.view(B, L, -1) if self.out_rows is None else h32
 
     def backward(self, dout):

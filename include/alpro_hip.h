@@ -610,6 +610,18 @@ size_t alpro_sim_topk_workspace_bytes(int nq, int ng, int k, int chunk);
 int alpro_sim_topk(const float* q, int nq, const float* g, int ng, int d, int k, float scale, int chunk, float* out_val, int32_t* out_idx,
                    void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- attention probabilities on request (BertModel.forward output_attentions; xbert.py:323,343) ----
+ * out[b][h][q - q0][k - k0] = exp(scale * <q_bhq, k_bhk> + key_bias[b][k] - lse[b][h][q]) for q0 <= q < q0 + nq, k0 <= k < k0 + nk: a window
+ * of the (L, L) softmax of every (sequence, head), fp32, (batch, H, nq, nk) contiguous.  qkv (batch*L, 3*H*64) as alpro_gemm wrote it
+ * (dtype: ALPRO_F32 / ALPRO_BF16 / ALPRO_F16, head_dim 64); lse (batch, H, L) fp32 as alpro_attn_fwd wrote it for the same qkv / scale /
+ * key_bias, 1 <= L <= ALPRO_ATTN_MAX_L; key_bias (batch, L) fp32 or NULL.  lse normalises over all L keys, so a window is a slice of the full
+ * map (never renormalised); any 0 <= q0, 1 <= nq, q0 + nq <= L (likewise k), no tile alignment needed.  These are the probabilities BEFORE
+ * dropout.  The exponential sees min(s - lse, 0) only: every element is in [0, 1], no inf / NaN for finite inputs.  16-bit operands use the
+ * 16-bit MFMA, fp32 the fp32 MFMA (exact products).  qkv and out 16-byte aligned.  Every argument is checked before the first HIP call.
+ * One launch, no atomics, no workspace: bitwise reproducible. */
+int alpro_attn_probs(const void* qkv, const float* lse, const float* key_bias, float* out, int dtype, int batch, int L, int H, float scale,
+                     int q0, int nq, int k0, int nk, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
