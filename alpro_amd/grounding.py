@@ -1,8 +1,12 @@
-"""Caption-to-region grounding maps from the fusion encoder's self-attention.
+"""Grounding maps from the encoders' self-attention: caption token -> region (fusion encoder), frame -> region and frame -> frame (visual encoder).
 
 The fusion layers attend over [text ; video tokens] (alpro_models.py:278-281), so the text-query x patch-key block of a fusion layer's softmax
 says which regions a caption token reads -- the map the ALBEF line of work visualises.  text_to_patch_attention returns that block alone:
 hip.attn_probs is asked for the window (text rows) x (patch keys) of every map, the (L, L) maps are never formed.
+
+The fusion maps are collapsed over time (the fusion encoder sees temporally pooled patch tokens).  Where the visual encoder itself looks, and in
+which frame, is in the maps of its divided space-time blocks: frame_patch_attention returns the frame's [CLS] query row of the spatial maps
+(again a window: no (1+N, 1+N) map is formed), patch_temporal_attention the (T, T) temporal map of every patch position.
 """
 import math
 
@@ -51,3 +55,69 @@ def text_to_patch_attention(model, text_input_ids, text_input_mask, video_embeds
         m = out.attentions[i].mean(dim=1)
         acc = m if acc is None else acc + m
     return (acc / float(len(pick))).view(B, Lt, hg, hg)
+
+
+def _visual_encoder(encoder, what):
+    enc = getattr(encoder, "visual_encoder", encoder)    # an AlproBaseModel, or the TimeSformer itself
+    if enc.training:
+        raise RuntimeError("%s inspects a trained model: call model.eval() first (no dropout, no drop-path, no RNG draw)" % what)
+    return enc
+
+
+def _grid(visual_inputs, what):
+    if visual_inputs.dim() != 5 or visual_inputs.shape[3] % 16 or visual_inputs.shape[4] % 16:
+        raise ValueError("%s: visual_inputs %s is not (B, T, C, H, W) with H and W multiples of the 16-pixel patch" % (what, tuple(visual_inputs.shape)))
+    B, T, _, H, W = visual_inputs.shape
+    return B, T, H // 16, W // 16
+
+
+def _block_mean(maps, layers, what):
+    pick = []
+    for l in layers:
+        i = int(l)
+        if not -len(maps) <= i < len(maps):
+            raise ValueError("%s: layer %d outside the %d blocks" % (what, i, len(maps)))
+        pick.append(i % len(maps))
+    if not pick:
+        raise ValueError("%s: no layer chosen" % what)
+    return pick
+
+
+@torch.no_grad()
+def frame_patch_attention(encoder, visual_inputs, layers=(-1,), reduce_heads="mean"):
+    """encoder: a TimeSformer, or any AlproBaseModel (its visual_encoder is used), in eval mode; visual_inputs (B, T, C, H, W) on the device, as
+    the models take them.  Returns (B, T, Hg, Wg) fp32: the probability the frame's [CLS] query puts on each patch of ITS frame in the spatial
+    attention, averaged over the heads and over the chosen blocks `layers` (negative: from the end; default: the last block).  Only the window
+    ((0, 1), (1, 1 + N)) of the chosen blocks' spatial maps is formed.  The [CLS] key is left out and nothing is renormalised: a frame's map
+    sums to the share of the [CLS] query's attention that goes to the patches."""
+    what = "frame_patch_attention"
+    enc = _visual_encoder(encoder, what)
+    if reduce_heads != "mean":
+        raise ValueError("%s: reduce_heads=%r (only 'mean')" % (what, reduce_heads))
+    B, T, hg, wg = _grid(visual_inputs, what)
+    depth = len(enc.model.blocks)
+    pick = sorted(set(_block_mean(range(depth), layers, what)))
+    out = enc.forward_features(visual_inputs.transpose(1, 2), output_attentions=True, attn_layers=pick, attn_window=((0, 1), (1, 1 + hg * wg)))
+    acc = None
+    for l in layers:   # (B*T, H, 1, N) each, in block order: head mean, then the layer mean
+        m = out.spatial_attentions[pick.index(int(l) % depth)].mean(dim=1)
+        acc = m if acc is None else acc + m
+    return (acc / float(len(layers))).view(B, T, hg, wg)
+
+
+@torch.no_grad()
+def patch_temporal_attention(encoder, visual_inputs, layers=(-1,)):
+    """As frame_patch_attention, for the temporal half: returns (B, Hg, Wg, T, T) fp32, the temporal attention map (query frame, key frame) of every
+    patch position, averaged over the heads and over the chosen blocks."""
+    what = "patch_temporal_attention"
+    enc = _visual_encoder(encoder, what)
+    B, T, hg, wg = _grid(visual_inputs, what)
+    depth = len(enc.model.blocks)
+    pick = sorted(set(_block_mean(range(depth), layers, what)))
+    # (the spatial maps come with the flag: keep them to one element per frame and head)
+    out = enc.forward_features(visual_inputs.transpose(1, 2), output_attentions=True, attn_layers=pick, attn_window=((0, 1), (0, 1)))
+    acc = None
+    for l in layers:   # (B*N, H, T, T) each
+        m = out.temporal_attentions[pick.index(int(l) % depth)].mean(dim=1)
+        acc = m if acc is None else acc + m
+    return (acc / float(len(layers))).view(B, hg, wg, T, T)

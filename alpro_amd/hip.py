@@ -32,7 +32,7 @@ EXPORTS = ["alpro_hip_last_error", "alpro_hip_abi_version", "alpro_hip_set_optio
            "alpro_hip_sched_workspace_bytes", "alpro_hip_set_sched_workspace", "alpro_hip_release_stream", "alpro_gemm_qkv_tattn", "alpro_add_layernorm_pre_mlp2", "alpro_adamw_step_lp",
            "alpro_gemm_rows_f32_relu_mask", "alpro_clip_pool", "alpro_adamw_step_groups", "alpro_attn_temporal_fwd_drop", "alpro_attn_temporal_bwd_drop",
            "alpro_vit_final_pool_mode", "alpro_vit_final_pool_mode_bwd", "alpro_augment_stage", "alpro_augment_stats", "alpro_resized_crop",
-           "alpro_sim_topk", "alpro_sim_topk_workspace_bytes", "alpro_attn_probs"]
+           "alpro_sim_topk", "alpro_sim_topk_workspace_bytes", "alpro_attn_probs", "alpro_attn_temporal_probs"]
 
 
 class GemmDesc(ctypes.Structure):
@@ -163,6 +163,7 @@ def load():
     lib.alpro_sim_topk_workspace_bytes.restype = ctypes.c_size_t
     lib.alpro_sim_topk.argtypes = [vp, i32, vp, i32, i32, i32, f32, i32, vp, vp, vp, ctypes.c_size_t, vp]
     lib.alpro_attn_probs.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, i32, i32, i32, vp]
+    lib.alpro_attn_temporal_probs.argtypes = [vp, vp, vp, i32, i64, i32, i32, f32, vp]
     if lib.alpro_hip_abi_version() != ABI_VERSION:
         raise RuntimeError("libalpro_hip.so ABI version mismatch")
     _lib = lib
@@ -675,6 +676,28 @@ def attn_probs(qkv, lse, batch, L, H, scale, key_bias=None, q_range=None, k_rang
     out = torch.empty((batch, H, max(nq, 0), max(nk, 0)), dtype=torch.float32, device=qkv.device)
     _check(lib.alpro_attn_probs(_ptr(qkv), _ptr(lse), _ptr(key_bias), _ptr(out), _CODE[qkv.dtype], batch, L, H, float(scale), q0, nq, k0, nk, _stream()),
            "alpro_attn_probs")
+    return out
+
+
+def attn_temporal_probs(qkv, lse, T, H, scale):
+    """The softmax probabilities attn_temporal() / gemm_qkv_tattn() never materialise (alpro_attn_temporal_probs): qkv (rows, 3*H*64) as the temporal
+    qkv Linear wrote it, lse ((rows + 31) // 32, H, 32) fp32 from attn_temporal(..., want_lse=True) or gemm_qkv_tattn(..., want_qkv=True) on the same
+    rows / scale -> (rows // T, H, T, T) fp32: group g is the rows g*T .. g*T + T - 1.  The probabilities before dropout."""
+    for name, t in (("qkv", qkv), ("lse", lse)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError("attn_temporal_probs: %s must be a device tensor (got %s): the hot path has no CPU fallback" % (name, getattr(t, "device", type(t))))
+    lib = load()
+    T, H = int(T), int(H)
+    if qkv.dtype not in _CODE or qkv.dim() != 2 or qkv.shape[1] != 3 * H * 64 or not qkv.is_contiguous():
+        raise RuntimeError("attn_temporal_probs: qkv must be a contiguous (rows, 3*H*64) = (rows, %d) fp32 / bf16 / fp16 tensor (got %s %s, strides %s)"
+                           % (3 * H * 64, qkv.dtype, tuple(qkv.shape), tuple(qkv.stride())))
+    rows = qkv.shape[0]
+    if lse.dtype != torch.float32 or tuple(lse.shape) != ((rows + 31) // 32, H, 32) or not lse.is_contiguous():
+        raise RuntimeError("attn_temporal_probs: lse must be a contiguous ((rows + 31) // 32, H, 32) = (%d, %d, 32) fp32 tensor (got %s %s)"
+                           % ((rows + 31) // 32, H, lse.dtype, tuple(lse.shape)))
+    # (the library refuses T outside 1..128 and rows % T != 0; max(.., 1): such a call never divides by zero here)
+    out = torch.empty((rows // max(T, 1), H, max(T, 0), max(T, 0)), dtype=torch.float32, device=qkv.device)
+    _check(lib.alpro_attn_temporal_probs(_ptr(qkv), _ptr(lse), _ptr(out), _CODE[qkv.dtype], rows, T, H, float(scale), _stream()), "alpro_attn_temporal_probs")
     return out
 
 

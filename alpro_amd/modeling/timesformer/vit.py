@@ -19,6 +19,9 @@ arguments, `forward_features` signatures and the state_dict layout (`model.block
   norm2 + Mlp + residual (:198-212)                    LayerNorm -> alpro_gemm(GELU) -> alpro_gemm(residual)
   norm (:372) + temporal mean pool (:484-492)          alpro_vit_final_pool
   DropPath per (b n)/(b t)/b rows (vit_utils.py:137)   row_scale vector in the GEMM epilogue
+  forward hooks on attn.attn_drop / temporal_attn      forward_features(output_attentions=, output_hidden_states=): the maps are
+  .attn_drop (the softmax of :92-93) and on the blocks  recomputed from q | k | v and the log-sum-exp rows (alpro_attn_probs,
+                                                       alpro_attn_temporal_probs), the hidden states are copies -> VisualEncoderOutput
 """
 import math
 from functools import partial
@@ -159,7 +162,91 @@ def _draws_per_call(blk):
     return blk.attn.attn_drop.p > 0 or blk.temporal_attn.attn_drop.p > 0 or (live_dp and not getattr(blk, "_presampled", None))
 
 
-def run_prefix_blocks(blocks, tok, B, T, W):
+class VisualEncoderOutput:
+    """What forward_features returns when output_attentions or output_hidden_states is set.
+      features             what the call returns without the flags (still differentiable when the call is anchored)
+      hidden_states        depth + 1 fp32 tensors (B, 1 + N*T, D): the embedding output (= the input of block 0), then every block's output; tokens
+                           in the reference's order b (h w t) behind the CLS row; before the final norm and the pooling.  None if not asked for
+      spatial_attentions   one (B*T, H, 1+N, 1+N) fp32 tensor per collected block (or its attn_window), batch index b*T + t, key / query 0 = the
+                           frame's copy of CLS.  None if not asked for
+      temporal_attentions  one (B*N, H, T, T) fp32 tensor per collected block, batch index b*N + n.  None if not asked for
+    The maps are what a forward pre-hook on the reference's attn.attn_drop / temporal_attn.attn_drop receives (the softmax before dropout);
+    all of them are detached copies."""
+    __slots__ = ("features", "hidden_states", "spatial_attentions", "temporal_attentions")
+
+    def __init__(self, features, hidden_states=None, spatial_attentions=None, temporal_attentions=None):
+        self.features, self.hidden_states = features, hidden_states
+        self.spatial_attentions, self.temporal_attentions = spatial_attentions, temporal_attentions
+
+
+class _Collector:
+    """The maps and hidden states of one forward_features call.  It only reads: no random draw, no write to anything the forward reads, every
+    launch on the launch stream.  Blocks are counted as they run (block_begin / block_end), so a frozen prefix and the anchored blocks behind it
+    share one object."""
+
+    def __init__(self, depth, output_attentions, output_hidden_states, attn_layers=None, attn_window=None):
+        self.want_attn, self.want_hidden = bool(output_attentions), bool(output_hidden_states)
+        if attn_layers is None:
+            self.layers = set(range(depth))
+        else:
+            self.layers = set()
+            for i in attn_layers:
+                i = int(i)
+                if not -depth <= i < depth:
+                    raise ValueError("attn_layers: block index %d outside -%d .. %d" % (i, depth, depth - 1))
+                self.layers.add(i % depth)
+        self.q_range = self.k_range = None
+        if attn_window is not None:
+            try:
+                (q0, q1), (k0, k1) = attn_window
+            except (TypeError, ValueError):
+                raise ValueError("attn_window must be ((q_start, q_stop), (k_start, k_stop)) over the 1 + N tokens of a frame (got %r)" % (attn_window,))
+            self.q_range, self.k_range = (int(q0), int(q1)), (int(k0), int(k1))
+        self.i = 0
+        self.hidden, self.spatial, self.temporal = [], [], []
+
+    def start(self, tok):
+        """The embedding output (nothing else writes it yet)."""
+        if self.want_hidden:
+            self.hidden.append(tok.detach().clone())
+
+    def block_begin(self):
+        """-> self if the block about to run collects its maps, else None."""
+        return self if (self.want_attn and self.i in self.layers) else None
+
+    def block_end(self, tok):
+        self.i += 1
+        if self.want_hidden:
+            _ClsSide.join(tok.device)   # a precise-CLS chain on its side stream still writes the block output's CLS rows
+            self.hidden.append(tok.detach().clone())
+
+    def add_temporal(self, qkv, lse, T, H, scale):
+        self.temporal.append(hip.attn_temporal_probs(qkv, lse, T, H, scale))
+
+    def add_spatial(self, qkv, lse, batch, L, H, scale):
+        self.spatial.append(hip.attn_probs(qkv, lse, batch, L, H, scale, q_range=self.q_range, k_range=self.k_range))
+
+    def result(self, features):
+        return VisualEncoderOutput(features, tuple(self.hidden) if self.want_hidden else None, tuple(self.spatial) if self.want_attn else None,
+                                   tuple(self.temporal) if self.want_attn else None)
+
+
+def _collector(depth, output_attentions, output_hidden_states, attn_layers, attn_window):
+    if not (output_attentions or output_hidden_states):
+        return None
+    return _Collector(depth, output_attentions, output_hidden_states, attn_layers, attn_window)
+
+
+def _run_collecting(blocks, tok, B, T, W, collect):
+    """The one-stream no-grad loop with a collector (never two half batches: nothing is collected across streams)."""
+    for blk in blocks:
+        tok = blk(tok, B, T, W, collect=collect.block_begin())
+        collect.block_end(tok)
+    _ClsSide.join(tok.device)
+    return tok
+
+
+def run_prefix_blocks(blocks, tok, B, T, W, collect=None):
     """The frozen prefix of a training forward (tr.frozen_prefix): the no-grad forward of `blocks`, in place -- nothing is saved for a backward
     and no W^T operand is built -- through run_blocks with what it brings (fused temporal launch, two half batches on two streams, deferred
     temporal add).  Train-mode stochasticity is the reference's: the drop-path masks are the ones sample_drop_paths drew for the whole step
@@ -167,6 +254,8 @@ def run_prefix_blocks(blocks, tok, B, T, W):
     the trainable blocks where the all-trainable step's does -- two half-batch calls would draw twice, so blocks that draw per call take the
     whole batch on the launch stream."""
     with torch.no_grad():
+        if collect is not None:
+            return _run_collecting(blocks, tok, B, T, W, collect)
         if any(_draws_per_call(blk) for blk in blocks):
             for blk in blocks:
                 tok = blk(tok, B, T, W)
@@ -175,7 +264,7 @@ def run_prefix_blocks(blocks, tok, B, T, W):
         return run_blocks(blocks, tok, B, T, W)
 
 
-def run_blocks(blocks, tok, B, T, W):
+def run_blocks(blocks, tok, B, T, W, collect=None):
     """The no-grad forward through `blocks` (tok updated in place and returned), CLS chains joined.
 
     Round 6: with alpro_amd.config.split_streams(B) the two halves of the batch go through every block on two HIP streams (clips are
@@ -187,6 +276,8 @@ def run_blocks(blocks, tok, B, T, W):
     (B = 32 x 8 frames: -1.3 ... -3.2 % per forward, profiles/r6_split_streams_ab.txt).  Outputs are those of the one-stream forward bit for
     bit as long as the half batch sends every Linear to the same GEMM kernel as the whole batch."""
     dev = tok.device
+    if collect is not None:
+        return _run_collecting(blocks, tok, B, T, W, collect)
     if not (tok.is_cuda and not torch.is_grad_enabled() and rt.split_streams(B)):
         for blk in blocks:
             tok = blk(tok, B, T, W)
@@ -362,16 +453,16 @@ class Block(nn.Module):
         seed_s = rt.next_dropout_seed() if ps > 0 else 0
         return (pt if seed_t else 0.0), seed_t, (ps if seed_s else 0.0), seed_s
 
-    def forward(self, x, B, T, W, drop_masks=None):
+    def forward(self, x, B, T, W, drop_masks=None, collect=None):
         """x: (B, 1 + N*T, D) fp32 contiguous token tensor; updated IN PLACE and returned (inference path).
         drop_masks: (temporal (B*N,), spatial (B*T,), MLP (B,)) drop-path row scales to apply instead of drawing them (run_blocks: a half batch's
-        rows of the masks drawn for the whole step)."""
-        return self._forward(x, B, T, drop_masks=drop_masks)
+        rows of the masks drawn for the whole step).  collect: the _Collector that takes this block's attention maps, or None."""
+        return self._forward(x, B, T, drop_masks=drop_masks, collect=collect)
 
-    def forward_train(self, x, B, T, W):
+    def forward_train(self, x, B, T, W, collect=None):
         """Same arithmetic as forward() but out of place: fresh buffers (the backward needs every LayerNorm input); returns (out, saved) for the
         explicit backward()."""
-        return self._forward(x, B, T, save=True)
+        return self._forward(x, B, T, save=True, collect=collect)
 
     def forward_cls(self, x, B, T, W):
         """LAST block when only the CLS output is consumed (the frozen prompter: get_pseudo_labels uses feat = proj(x[:, 0])):
@@ -380,7 +471,7 @@ class Block(nn.Module):
         (vit.py:165-212); eval mode only (no drop-path).  Returns the block output's CLS rows, (B, D) fp32."""
         return self._forward(x, B, T, cls_only=True)
 
-    def _forward(self, x, B, T, save=False, cls_only=False, drop_masks=None, replay=None, cls_precise=None):
+    def _forward(self, x, B, T, save=False, cls_only=False, drop_masks=None, replay=None, cls_precise=None, collect=None):
         """The divided space-time block (vit.py:146-212), every stage stated once.  The residual stream goes
             x --temporal branch--> xt --spatial branch--> x2 --MLP--> out
         and the three entry points differ in where those four live and in what is kept:
@@ -388,7 +479,11 @@ class Block(nn.Module):
             forward_train  save: a fresh tensor each, q | k | v, the log-sum-exp rows and gelu' kept -> (out, saved)
             forward_cls    cls_only: as forward up to the spatial attention, the rest on the CLS rows -> their (B, D) output rows
         replay (Block.replay): the kept subset of an earlier forward_train's saved dict; operand dtype, projection form, drop-path scales and
-        attention-dropout seeds are taken from it and nothing is drawn.  cls_precise: the precise-CLS decision of that earlier pass (None: read now)."""
+        attention-dropout seeds are taken from it and nothing is drawn.  cls_precise: the precise-CLS decision of that earlier pass (None: read now).
+        collect (a _Collector): the two attention maps of this block are recomputed from q | k | v and the log-sum-exp rows, which are then requested
+        from the kernels in inference too (extra stores only; the attention outputs keep their bits), on the launch stream, before those temporaries go."""
+        assert collect is None or not cls_only, "forward_cls collects nothing"
+        keep = save or collect is not None   # q | k | v and the log-sum-exp rows are wanted
         dt = replay["dt"] if replay is not None else rt.compute_dtype()
         S, D = x.shape[1], x.shape[2]
         N = (S - 1) // T
@@ -420,13 +515,17 @@ class Block(nn.Module):
             # round 6: qkv Linear + frame attention in one launch, q | k | v consumed out of the accumulators (alpro_gemm_qkv_tattn).  No-grad: the
             # (B*N*T, 2304) tensor is never written.  Training (ALPRO_FUSE_TATTN=1; off by default: alpro_amd/config.py): q | k | v are still
             # written (the backward reads them), what goes away is the attention launch and its re-read
-            r = hip.gemm_qkv_tattn(h, w_qkv, ta.qkv.bias, T, H, ta.scale, want_qkv=save)
-            a_t, qkv_t, lse_t = r if save else (r, None, None)
+            r = hip.gemm_qkv_tattn(h, w_qkv, ta.qkv.bias, T, H, ta.scale, want_qkv=keep)
+            a_t, qkv_t, lse_t = r if keep else (r, None, None)
         else:
             qkv_t = hip.gemm(h, w_qkv, bias=ta.qkv.bias)
-            r = hip.attn_temporal(qkv_t, T, H, ta.scale, want_lse=save, drop_p=ap_t, drop_seed=seed_t)
-            a_t, lse_t = r if save else (r, None)
+            r = hip.attn_temporal(qkv_t, T, H, ta.scale, want_lse=keep, drop_p=ap_t, drop_seed=seed_t)
+            a_t, lse_t = r if keep else (r, None)
         del r
+        if collect is not None:   # (B*N, H, T, T): the softmax before dropout
+            collect.add_temporal(qkv_t, lse_t, T, H, ta.scale)
+            if not save:
+                qkv_t = lse_t = None
         # ---- temporal projection, x -> xt, norm1 in frame-token order (vit.py:157-172, 180)
         pr = None
         if merged:
@@ -464,10 +563,14 @@ class Block(nn.Module):
             cq = dict(cls_q=cls_q, cls_group=T, cls_out=o_c_buf)
         elif cp:
             cq = dict(cls_q=self._cls_qkv(x_cls_in), cls_group=T)
-        r = hip.attn(qkv_s, B * T, N + 1, H, sa.scale, want_lse=save, drop_p=ap_s, drop_seed=seed_s, **cq)
+        r = hip.attn(qkv_s, B * T, N + 1, H, sa.scale, want_lse=keep, drop_p=ap_s, drop_seed=seed_s, **cq)
         r = r if isinstance(r, tuple) else (r,)   # out [, lse] [, cls_out]
-        a_s, lse_s, o_c = r[0], (r[1] if save else None), (r[-1] if cp else None)
+        a_s, lse_s, o_c = r[0], (r[1] if keep else None), (r[-1] if cp else None)
         del r, cq
+        if collect is not None:   # (B*T, H, 1+N, 1+N) or its window; with precise CLS rows the CLS query row is the 16-bit graph's
+            collect.add_spatial(qkv_s, lse_s, B * T, N + 1, H, sa.scale)
+            if not save:
+                lse_s = None
         if side is not None and not save:
             ev_mid = torch.cuda.current_stream().record_event()   # o_c is written
         # ---- spatial projection, xt -> x2, norm2 (vit.py:184-200)
@@ -954,12 +1057,17 @@ class VisionTransformer(nn.Module):
         emb = list(self.patch_embed.parameters()) + [self.cls_token, self.pos_embed, self.time_embed]
         return [emb] + [list(blk.parameters()) for blk in self.blocks]
 
-    def forward_features(self, x, return_all_tokens=False):
+    def forward_features(self, x, return_all_tokens=False, output_attentions=False, output_hidden_states=False, attn_layers=None, attn_window=None):
+        """The four keywords are TimeSformer.forward_features' (a VisualEncoderOutput when a flag is set; inference path)."""
         B = x.shape[0]
+        collect = _collector(len(self.blocks), output_attentions, output_hidden_states, attn_layers, attn_window)
         tok, T, W, N = self._embed(x)
-        tok = run_blocks(self.blocks, tok, B, T, W)
+        if collect is not None:
+            collect.start(tok)
+        tok = run_blocks(self.blocks, tok, B, T, W, collect=collect)
         y = hip.layernorm(tok, self.norm.weight, self.norm.bias, VIT_EPS, torch.float32).view(B, -1, self.embed_dim)
-        return y if return_all_tokens else y[:, 0]
+        y = y if return_all_tokens else y[:, 0]
+        return y if collect is None else collect.result(y)
 
     def forward(self, x):
         raise NotImplementedError("the Kinetics classification head is outside ALPRO's video-text path")
@@ -1010,14 +1118,28 @@ class TimeSformer(nn.Module):
 
     POOLING = {'temporal': hip.POOL_TEMPORAL, 'spatial': hip.POOL_SPATIAL, 'none': hip.POOL_NONE}   # vit.py:489
 
-    def forward_features(self, x, return_all_tokens=True, pooling='temporal'):
+    def forward_features(self, x, return_all_tokens=True, pooling='temporal', output_attentions=False, output_hidden_states=False, attn_layers=None,
+                         attn_window=None):
         """x: (b, c, t, h, w); the final LayerNorm fused with the pooling (vit.py:475-503), n = h*w/256 patches per frame:
           'temporal' -> (b, 1 + n, 768)     CLS, then every patch averaged over the frames
           'spatial'  -> (b, 1 + t, 768)     CLS, then every frame averaged over its patches
           'none'     -> (b, t, 1 + n, 768)  every patch of every frame, the clip's CLS token in front of each frame
         The reference reshapes the tokens by the CONFIG's img_size / num_frm (vit.py:481-487), so an input of another geometry raises there; here
         it raises too in the two frame-resolved modes (the temporal mode keeps taking the resampled geometries the ALPRO models feed it).
-        With autograd enabled the whole encoder is one autograd node with a hand-written backward."""
+        With autograd enabled the whole encoder is one autograd node with a hand-written backward.
+
+        output_attentions / output_hidden_states: return a VisualEncoderOutput (features = the value above, plus the hidden states and the spatial /
+        temporal attention maps of the 12 divided space-time blocks: see that class) -- what forward hooks on the reference's blocks and on their
+        attn.attn_drop / temporal_attn.attn_drop modules receive.  The forward is flash-style, so the maps are recomputed per block from its
+        q | k | v and log-sum-exp rows (alpro_attn_probs, alpro_attn_temporal_probs) and the hidden states are copies; all are detached, the maps are
+        the softmax BEFORE attention dropout, drop-path shows in the hidden states only.  With both flags off nothing of this runs.  Asking changes
+        no bit of `features`, of a gradient or of a random stream, with one exception of schedule: an even batch of 16 clips or more runs as ONE
+        stream (as under config.set_split_streams(False)), not as two half batches.  With precise [CLS] rows the CLS query row of a spatial map is
+        the 16-bit graph's while the hidden states' CLS rows carry the fp32 re-evaluation.
+        attn_layers: block indices (negative: from the end) whose maps are collected; None = all 12.  Mind the size: the full set at B = 8 clips of
+        8 frames at 224 px is 12 x (64, 12, 197, 197) fp32 = 1.4 GB of spatial maps.
+        attn_window: ((q_start, q_stop), (k_start, k_stop)) over the 1 + N tokens of a frame: only this window of every spatial map is formed, bit
+        for bit the slice of the full map (the temporal maps are always whole)."""
         assert return_all_tokens, "forward_features(return_all_tokens=False) is not supported (the reference fails on it: vit.py:484 indexes the 2-D CLS tensor with three subscripts)"
         assert pooling in ['temporal', 'spatial', 'none'], 'Invalid pooling type {}'.format(pooling)
         mode = self.POOLING[pooling]
@@ -1027,31 +1149,38 @@ class TimeSformer(nn.Module):
                 raise RuntimeError("forward_features(pooling=%r): the input has %d frames of %d x %d patches, the config (num_frm=%d, img_size=%d) says %d frames of "
                                    "%d x %d -- the reference's rearrange (vit.py:487) fails on this input too" % (pooling, t, h // self.patch_size, w // self.patch_size,
                                                                                                                self.num_frames, self.img_size, self.num_frames, G, G))
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            return tr.run_anchored(_VisualRun(self, mode), [x], list(self.parameters()))
         m = self.model
+        collect = _collector(len(m.blocks), output_attentions, output_hidden_states, attn_layers, attn_window)
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            out = tr.run_anchored(_VisualRun(self, mode, collect), [x], list(self.parameters()))
+            return out if collect is None else collect.result(out)
         B = x.shape[0]
         in_step = torch.is_grad_enabled()   # a wholly frozen encoder inside a training step: the frozen prefix is the whole encoder
         with torch.no_grad():               # (run_blocks forks its two half-batch streams only without grad)
             tok, T, W, N = m._embed(x)
+            if collect is not None:
+                collect.start(tok)
             if in_step:   # as _VisualRun.forward treats a prefix: the step's drop-path masks in one draw, one pair of dropout seeds per block
                 if B * N != B * T and B * T != B:
                     sample_drop_paths(m.blocks, B, T, N, tok.device)
-                tok = run_prefix_blocks(m.blocks, tok, B, T, W)
+                tok = run_prefix_blocks(m.blocks, tok, B, T, W, collect=collect)
                 for blk in m.blocks:
                     blk._presampled = None
             else:
-                tok = run_blocks(m.blocks, tok, B, T, W)
+                tok = run_blocks(m.blocks, tok, B, T, W, collect=collect)
             if mode == hip.POOL_TEMPORAL:
                 out32, _ = hip.vit_final_pool(tok, m.norm.weight, m.norm.bias, VIT_EPS, B, T, N, torch.float32)
             else:
                 out32, _ = hip.vit_final_pool_mode(tok, m.norm.weight, m.norm.bias, VIT_EPS, B, T, N, torch.float32, mode)
-        return out32
+        return out32 if collect is None else collect.result(out32)
 
-    def forward_cls(self, x):
+    def forward_cls(self, x, **flags):
         """x: (b, c, t, h, w) -> (b, 768): the CLS row of forward_features(x) only, inference only.  The last block's spatial
         projection and MLP run on the CLS rows alone (Block.forward_cls); used by the frozen prompter, whose pseudo labels
         depend on nothing else (alpro_models.py:531-551)."""
+        if flags:
+            raise TypeError("forward_cls takes no %s: its last block runs on the CLS rows alone, so it has neither whole hidden states nor the last "
+                            "block's maps -- use forward_features(..., output_attentions=True / output_hidden_states=True)" % ", ".join(sorted(flags)))
         assert not torch.is_grad_enabled(), "forward_cls is an inference path"
         m = self.model
         B = x.shape[0]
@@ -1075,8 +1204,9 @@ class TimeSformer(nn.Module):
 class _VisualRun:
     """Forward/backward of the whole visual encoder for tr.Anchor (alpro_models.py:186-194 under autograd)."""
 
-    def __init__(self, enc, mode=hip.POOL_TEMPORAL):
+    def __init__(self, enc, mode=hip.POOL_TEMPORAL, collect=None):
         self.enc, self.mode = enc, mode   # mode: the pooling behind the final norm (hip.POOL_*)
+        self.collect = collect            # a _Collector (output_attentions / output_hidden_states) or None
 
     def forward(self, x):
         m = self.enc.model
@@ -1086,6 +1216,9 @@ class _VisualRun:
         k = tr.frozen_prefix(m.stage_params(), torch.is_tensor(x) and x.requires_grad)
         self.nfro, self.embed_frozen = max(k - 1, 0), k >= 1
         tok, T, W, N = m._embed(x)
+        collect, self.collect = self.collect, None   # (nothing of it is needed in backward)
+        if collect is not None:
+            collect.start(tok)
         self.rows, self.dims, self.Wg = (None if self.embed_frozen else m._last_rows), (B, T, N), W
         if self.embed_frozen:
             m._last_rows = None   # (the patch rows are the weight gradient's operand: nobody reads them)
@@ -1097,12 +1230,14 @@ class _VisualRun:
         if B * N != B * T and B * T != B:  # (the table is keyed by row count: the three counts must differ, else draw per call)
             sample_drop_paths(m.blocks, B, T, N, tok.device)
         if self.nfro:
-            tok = run_prefix_blocks(m.blocks[:self.nfro], tok, B, T, W)
+            tok = run_prefix_blocks(m.blocks[:self.nfro], tok, B, T, W, collect=collect)
             for blk in m.blocks[:self.nfro]:
                 blk._presampled = None
         for blk in m.blocks[self.nfro:]:
-            tok, sv = blk.forward_train(tok, B, T, W)
+            tok, sv = blk.forward_train(tok, B, T, W, collect=collect.block_begin() if collect is not None else None)
             blk._presampled = None
+            if collect is not None:   # (the maps are already taken, inside the block: before the saved dict is cut down below)
+                collect.block_end(tok)
             if self.recompute:
                 _ClsSide.join(tok.device)   # a precise-CLS chain on its side stream still writes x2's CLS rows: it is through before x2 is released
                 sv, full = Block.slim_saved(sv), sv

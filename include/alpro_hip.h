@@ -622,6 +622,17 @@ int alpro_sim_topk(const float* q, int nq, const float* g, int ng, int d, int k,
 int alpro_attn_probs(const void* qkv, const float* lse, const float* key_bias, float* out, int dtype, int batch, int L, int H, float scale,
                      int q0, int nq, int k0, int nk, void* stream);
 
+/* ---- temporal attention probabilities on request (TimeSformer.forward_features output_attentions; vit.py:92-93 on the view of vit.py:147) ----
+ * P[g, h, q, k] = exp(scale * <q_(g*T+q, h), k_(g*T+k, h)> - lse[row g*T+q, head h]),  fp32, out (rows / T, H, T, T).
+ * qkv (rows, 3*H*64) as the temporal qkv Linear (or alpro_gemm_qkv_tattn's qkv_out) wrote it; lse in the layout alpro_attn_temporal_fwd and
+ * alpro_gemm_qkv_tattn write: ((rows + 31) / 32, H, 32), row c*32 + r of head h at [c, h, r].  1 <= T <= ALPRO_ATTN_MAX_T, rows a multiple of T
+ * (need not be a multiple of 32).  Pre-dropout probabilities; no dropout arguments.  T dividing 32: a wave forms the 32 x 32 S^T of a 32-row
+ * unit (32 / T whole groups) against itself and stores the same-group entries; any other T: 32 x 32 tiles per (group, head).  The exponential
+ * sees min(s - lse, 0) only: every element is in [0, 1], no inf / NaN for finite inputs.  16-bit operands use the 16-bit MFMA, fp32 the fp32
+ * MFMA (exact products).  qkv and out 16-byte aligned; rows == 0 is a no-op.  Every argument is checked before the first HIP call.  One launch,
+ * no atomics, no workspace: bitwise reproducible. */
+int alpro_attn_temporal_probs(const void* qkv, const float* lse, float* out, int dtype, int64_t rows, int T, int H, float scale, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
