@@ -57,6 +57,69 @@ def text_to_patch_attention(model, text_input_ids, text_input_mask, video_embeds
     return (acc / float(len(pick))).view(B, Lt, hg, hg)
 
 
+def text_to_patch_gradcam(model, text_input_ids, text_input_mask, video_embeds, layers=(-1,), target=1, grad_scale=None):
+    """Grad-CAM of the ITM score over the patches, per caption token: arguments as text_to_patch_attention; returns (B, Lt, Hg, Wg) fp32,
+    P * relu(d score / d P) of the text-query x patch-key block of the chosen fusion `layers`, averaged over the heads, then over the layers,
+    with score = itm_head(fusion [CLS])[:, target].sum() (target 1: "match") and P the softmax before dropout.  This is the map the ALBEF line
+    of work visualises; the raw attention (text_to_patch_attention) says where a token reads, this one which regions made the caption match.
+    The text pass runs without grad, the fusion pass over [text ; video] with a detached copy of video_embeds that requires a gradient, and
+    an AttnGradients collector takes the window ((0, Lt), (Lt + 1, Lt + Lv)) from the layers' backward: no (L, L) tensor is formed.
+
+    The model is left untouched: every parameter's requires_grad is False for the duration (no weight-gradient launch, no .grad, no flat
+    optimizer buffer is written) and restored afterwards.  The call runs an anchored backward, so it bumps train.BACKWARD_EPOCH: it must not
+    sit between an optimizer's synchronize() and step().
+    grad_scale: fp16 operands need a scaled backward (activation gradients underflow otherwise): the score is multiplied by grad_scale, the
+    kernel divides G by it; a power of two, so the rescale is exact.  None: the initial scale of alpro_amd.amp.LossScaler under fp16, 1 under
+    bf16 / fp32.  A non-finite map raises (fp16: lower grad_scale); there is no retry."""
+    from alpro_amd import config as rt
+    from alpro_amd.modeling.alpro_models import _linear32
+    from alpro_amd.modeling.xbert import AttnGradients
+    what = "text_to_patch_gradcam"
+    if model.training:
+        raise RuntimeError("%s inspects a trained model: call model.eval() first (no dropout, no RNG draw)" % what)
+    B, Lt = text_input_ids.shape
+    Lv = video_embeds.shape[1] if video_embeds.dim() == 3 else 0
+    hg = math.isqrt(Lv - 1) if Lv > 1 else 0
+    if video_embeds.dim() != 3 or video_embeds.shape[0] != B or hg < 1 or hg * hg != Lv - 1:
+        raise ValueError("%s: video_embeds %s is not (B=%d, 1 + Hg*Wg, D) with a square patch grid" % (what, tuple(video_embeds.shape), B))
+    if grad_scale is None:
+        from alpro_amd.amp import LossScaler
+        grad_scale = LossScaler()._init if rt.compute_dtype() == torch.float16 else 1.0
+    grad_scale = float(grad_scale)
+    if not grad_scale > 0 or math.frexp(grad_scale)[0] != 0.5:
+        raise ValueError("%s: grad_scale=%r is not a positive power of two (the rescale of the gradient must be exact)" % (what, grad_scale))
+    bert = getattr(model.text_encoder, "bert", model.text_encoder)    # BertForMaskedLM, or the bare BertModel of the QA model
+    lo, hi = bert.encoder.layer_range("fusion")
+    pick = _layer_indices(layers, hi - lo)
+    collector = AttnGradients(layers=pick, window=((0, Lt), (Lt + 1, Lt + Lv)), want=("cam",), grad_scale=grad_scale)
+    flags = [(p, p.requires_grad) for p in model.parameters()]
+    try:
+        for p, _ in flags:
+            p.requires_grad_(False)
+        with torch.no_grad():
+            text_embeds = model._text_embeds(text_input_ids, text_input_mask)
+        video = video_embeds.detach().to(text_embeds.dtype).clone().requires_grad_(True)
+        video_atts = torch.ones((B, Lv), dtype=text_input_mask.dtype, device=text_input_mask.device)
+        with torch.enable_grad():
+            out = bert(encoder_embeds=torch.cat([text_embeds, video], dim=1), attention_mask=torch.cat([text_input_mask, video_atts], dim=1),
+                       return_dict=True, mode="fusion", attn_grads=collector).last_hidden_state
+            score = _linear32(out[:, 0, :], model.itm_head)[:, int(target)].sum() * grad_scale
+            with rt.loss_scaling(collector):   # (marks the backward as scaled: config.check_backward_precision)
+                score.backward()
+    finally:
+        for p, f in flags:
+            p.requires_grad_(f)
+    acc = None
+    for i in pick:   # (B, H, Lt, Hg*Wg) each: head mean, then the layer mean
+        m = collector.cams[i].mean(dim=1)
+        acc = m if acc is None else acc + m
+    res = (acc / float(len(pick))).view(B, Lt, hg, hg)
+    if not bool(torch.isfinite(res).all()):
+        raise RuntimeError("%s: the map is not finite at grad_scale=%g -- the scaled backward left fp16's range; pass a smaller power of two as grad_scale"
+                           % (what, grad_scale))
+    return res
+
+
 def _visual_encoder(encoder, what):
     enc = getattr(encoder, "visual_encoder", encoder)    # an AlproBaseModel, or the TimeSformer itself
     if enc.training:

@@ -32,7 +32,7 @@ EXPORTS = ["alpro_hip_last_error", "alpro_hip_abi_version", "alpro_hip_set_optio
            "alpro_hip_sched_workspace_bytes", "alpro_hip_set_sched_workspace", "alpro_hip_release_stream", "alpro_gemm_qkv_tattn", "alpro_add_layernorm_pre_mlp2", "alpro_adamw_step_lp",
            "alpro_gemm_rows_f32_relu_mask", "alpro_clip_pool", "alpro_adamw_step_groups", "alpro_attn_temporal_fwd_drop", "alpro_attn_temporal_bwd_drop",
            "alpro_vit_final_pool_mode", "alpro_vit_final_pool_mode_bwd", "alpro_augment_stage", "alpro_augment_stats", "alpro_resized_crop",
-           "alpro_sim_topk", "alpro_sim_topk_workspace_bytes", "alpro_attn_probs", "alpro_attn_temporal_probs"]
+           "alpro_sim_topk", "alpro_sim_topk_workspace_bytes", "alpro_attn_probs", "alpro_attn_temporal_probs", "alpro_attn_probs_grad"]
 
 
 class GemmDesc(ctypes.Structure):
@@ -164,6 +164,7 @@ def load():
     lib.alpro_sim_topk.argtypes = [vp, i32, vp, i32, i32, i32, f32, i32, vp, vp, vp, ctypes.c_size_t, vp]
     lib.alpro_attn_probs.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, i32, i32, i32, vp]
     lib.alpro_attn_temporal_probs.argtypes = [vp, vp, vp, i32, i64, i32, i32, f32, vp]
+    lib.alpro_attn_probs_grad.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, i32, i32, i32, i32, vp]
     if lib.alpro_hip_abi_version() != ABI_VERSION:
         raise RuntimeError("libalpro_hip.so ABI version mismatch")
     _lib = lib
@@ -677,6 +678,39 @@ def attn_probs(qkv, lse, batch, L, H, scale, key_bias=None, q_range=None, k_rang
     _check(lib.alpro_attn_probs(_ptr(qkv), _ptr(lse), _ptr(key_bias), _ptr(out), _CODE[qkv.dtype], batch, L, H, float(scale), q0, nq, k0, nk, _stream()),
            "alpro_attn_probs")
     return out
+
+
+def attn_probs_grad(qkv, dctx, lse, batch, L, H, scale, key_bias=None, q_range=None, k_range=None, want=("grad", "cam"), grad_scale=1.0):
+    """The gradient w.r.t. the softmax probabilities that attn_bwd() never materialises, and the Grad-CAM map (alpro_attn_probs_grad):
+    qkv / lse / key_bias / the windows as for attn_probs; dctx (batch*L, H*64) in qkv's dtype, the gradient w.r.t. attn()'s output as
+    attn_bwd() takes it.  want: "grad" -> G = grad_scale * dctx . v, "cam" -> P * max(G, 0) with P bitwise attn_probs' value; returns the
+    requested (batch, H, nq, nk) fp32 tensors in the order of `want` (a single tensor for a single name).  The eval-mode gradient: the
+    pre-dropout softmax's, no dropout arguments."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or len(set(want)) != len(want) or any(w not in ("grad", "cam") for w in want):
+        raise RuntimeError("attn_probs_grad: want=%r (one or both of 'grad', 'cam', each once)" % (want,))
+    for name, t in (("qkv", qkv), ("dctx", dctx), ("lse", lse)) + ((("key_bias", key_bias),) if key_bias is not None else ()):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError("attn_probs_grad: %s must be a device tensor (got %s): the hot path has no CPU fallback" % (name, getattr(t, "device", type(t))))
+    lib = load()
+    batch, L, H = int(batch), int(L), int(H)
+    if qkv.dtype not in _CODE or qkv.dim() != 2 or tuple(qkv.shape) != (batch * L, 3 * H * 64) or not qkv.is_contiguous():
+        raise RuntimeError("attn_probs_grad: qkv must be a contiguous (batch*L, 3*H*64) = (%d, %d) fp32 / bf16 / fp16 tensor (got %s %s, strides %s)"
+                           % (batch * L, 3 * H * 64, qkv.dtype, tuple(qkv.shape), tuple(qkv.stride())))
+    if dctx.dtype != qkv.dtype or tuple(dctx.shape) != (batch * L, H * 64) or not dctx.is_contiguous():
+        raise RuntimeError("attn_probs_grad: dctx must be a contiguous (batch*L, H*64) = (%d, %d) %s tensor, the dtype of qkv (got %s %s, strides %s)"
+                           % (batch * L, H * 64, qkv.dtype, dctx.dtype, tuple(dctx.shape), tuple(dctx.stride())))
+    if lse.dtype != torch.float32 or tuple(lse.shape) != (batch, H, L) or not lse.is_contiguous():
+        raise RuntimeError("attn_probs_grad: lse must be a contiguous (batch, H, L) = (%d, %d, %d) fp32 tensor (got %s %s)" % (batch, H, L, lse.dtype, tuple(lse.shape)))
+    if key_bias is not None and (key_bias.dtype != torch.float32 or tuple(key_bias.shape) != (batch, L) or not key_bias.is_contiguous()):
+        raise RuntimeError("attn_probs_grad: key_bias must be a contiguous (batch, L) = (%d, %d) fp32 tensor (got %s %s)" % (batch, L, key_bias.dtype, tuple(key_bias.shape)))
+    (q0, nq), (k0, nk) = _window(q_range, L), _window(k_range, L)
+    # (the library refuses a window outside 0..L or an empty one; max(.., 0): such a call never allocates a negative size)
+    outs = {w: torch.empty((batch, H, max(nq, 0), max(nk, 0)), dtype=torch.float32, device=qkv.device) for w in want}
+    _check(lib.alpro_attn_probs_grad(_ptr(qkv), _ptr(dctx), _ptr(lse), _ptr(key_bias), _ptr(outs.get("grad")), _ptr(outs.get("cam")), _CODE[qkv.dtype],
+                                     batch, L, H, float(scale), float(grad_scale), q0, nq, k0, nk, _stream()), "alpro_attn_probs_grad")
+    res = tuple(outs[w] for w in want)
+    return res if len(res) > 1 else res[0]
 
 
 def attn_temporal_probs(qkv, lse, T, H, scale):

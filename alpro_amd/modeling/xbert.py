@@ -57,6 +57,23 @@ class BertSelfAttention(nn.Module):
         self.key = nn.Linear(config.hidden_size, self.all_head_size)
         self.value = nn.Linear(config.hidden_size, self.all_head_size)
         self.dropout = nn.Dropout(config.attention_probs_dropout_prob)
+        # xbert.py:243-255: with the flag set the layer keeps its full (B, H, L, L) fp32 softmax in forward (hip.attn_probs) and the gradient of
+        # whatever was differentiated w.r.t. it in backward (hip.attn_probs_grad).  The reference gates both on is_cross_attention, which ALPRO
+        # never runs; here they serve the self-attention.  False (the default): nothing runs.
+        self.save_attention = False
+        self.attention_map = self.attn_gradients = None
+
+    def save_attn_gradients(self, attn_gradients):
+        self.attn_gradients = attn_gradients
+
+    def get_attn_gradients(self):
+        return self.attn_gradients
+
+    def save_attention_map(self, attention_map):
+        self.attention_map = attention_map
+
+    def get_attention_map(self):
+        return self.attention_map
 
 
 class BertSelfOutput(nn.Module):
@@ -151,15 +168,20 @@ class BertLayer(nn.Module):
         return o32, o_t
 
     # ---- training path ---------------------------------------------------------------------------------
-    def forward_train(self, h32, h_t, key_bias, B, L, save=True, rows=None, tap=None):
+    def forward_train(self, h32, h_t, key_bias, B, L, save=True, rows=None, tap=None, attn_grads=None, pass_index=None):
         """rows (optional, LongTensor of flat row indices): the only rows of this layer's OUTPUT anybody reads (the last fusion layer: [CLS] rows, the
         MLM pairs' text rows, the positives' patch rows -- a quarter of the 4B x 237).  Attention still runs over every row (all keys / values are
         needed, and the kernel's unit is a whole sequence); everything behind it -- attention-output dense, both LayerNorms, the FFN -- is row-wise
         and runs on the gathered rows only; the outputs are then (len(rows), D).
-        tap (optional, _AttnTap): output_attentions -- receives this layer's softmax probabilities, one more launch on its own qkv / lse / key bias."""
+        tap (optional, _AttnTap): output_attentions -- receives this layer's softmax probabilities, one more launch on its own qkv / lse / key bias.
+        attn_grads (optional, AttnGradients) with pass_index, this layer's index in the pass: backward() hands the collector d(ctx) (BertModel.forward)."""
+        sa, so = self.attention.self, self.attention.output
+        watched = sa.save_attention or (attn_grads is not None and attn_grads.wants(pass_index))
+        if watched and self.training and float(self.config.attention_probs_dropout_prob) > 0:
+            raise RuntimeError("BertLayer: the gradient w.r.t. the attention probabilities is the eval-mode one (the softmax before dropout); "
+                               "attention_probs_dropout_prob=%g is active in train mode -- call model.eval() first" % float(self.config.attention_probs_dropout_prob))
         hp, seed1, seed2, ap, seed_a = self._drop()
         dt = rt.compute_dtype()
-        sa, so = self.attention.self, self.attention.output
         eps = self.config.layer_norm_eps
         H = sa.num_attention_heads
         scale = 1.0 / math.sqrt(sa.attention_head_size)
@@ -174,6 +196,8 @@ class BertLayer(nn.Module):
             ctx, lse = hip.attn(qkv, B, L, H, scale, key_bias, want_lse=True, drop_p=ap, drop_seed=seed_a)
         if tap is not None:   # the probabilities before dropout (xbert.py:323,343); with precise [CLS] rows the [CLS] query row is the 16-bit graph's
             tap.add(qkv, lse, B, L, H, scale, key_bias)
+        if sa.save_attention:   # xbert.py:325-326, for the self-attention
+            sa.save_attention_map(hip.attn_probs(qkv, lse, B, L, H, scale, key_bias))
         ctx_full, M_full = ctx, h_t.shape[0]
         if rows is not None and cp:
             raise RuntimeError("BertLayer: an output row subset is supported on the fusion layers only")
@@ -199,6 +223,8 @@ class BertLayer(nn.Module):
                 s2.view(B, L, D)[:, 0] = s2_c
         sv = dict(h_t=h_t, qkv=qkv, ctx=ctx, lse=lse, s1=s1, a_t=a_t, u=u, u_tiled=u_tiled, it=it, s2=s2, kb=key_bias, dims=(B, L, H, scale), dt=dt,
                   drop=(hp, seed1, seed2, ap, seed_a), rows=rows, ctx_full=ctx_full, M_full=M_full) if save else None
+        if save and attn_grads is not None:
+            sv["attn_grads"], sv["pass_index"] = attn_grads, pass_index
         return o32, o_t, sv
 
     def backward(self, sv, do32, do_t):
@@ -239,6 +265,12 @@ class BertLayer(nn.Module):
             full32 = torch.zeros((sv["M_full"], D), dtype=torch.float32, device=dev)
             full32.index_copy_(0, rows, ds1)
             ds1 = full32
+        # dctx is final here (rows nobody read hold zeros): the two taps on d(score) / d(P), P the softmax before dropout
+        collector = sv.get("attn_grads")
+        if collector is not None:
+            collector.add(sv["pass_index"], sv["qkv"], dctx, sv["lse"], sv["dims"], sv["kb"])
+        if sa.save_attention:   # xbert.py:327: what the reference's hook on attention_probs receives
+            sa.save_attn_gradients(hip.attn_probs_grad(sv["qkv"], dctx, sv["lse"], B, L, H, scale, sv["kb"], want=("grad",)))
         dqkv = hip.attn_bwd(sv["qkv"], sv["ctx_full"], dctx, sv["lse"], B, L, H, scale, sv["kb"], drop_p=ap, drop_seed=seed_a)
         # fused q/k/v projection: the three weight gradients come from the three column blocks of dqkv
         Hd = sa.all_head_size
@@ -271,6 +303,73 @@ class _AttnTap:
 
     def add(self, qkv, lse, B, L, H, scale, key_bias):
         self.maps.append(hip.attn_probs(qkv, lse, B, L, H, scale, key_bias, q_range=self.q_range, k_range=self.k_range))
+
+
+class AttnGradients:
+    """Collects, during backward(), the gradient of whatever is differentiated w.r.t. the attention probabilities of the layers of one pass
+    (BertModel.forward attn_grads): after the backward `grads[i]` = G = d(score) / d(P_i) and `cams[i]` = P_i * relu(G) -- the Grad-CAM map
+    of the ALBEF line of work --, (B, H, nq, nk) fp32 each, keyed by the layer's index i in the pass.  P_i is the softmax BEFORE dropout,
+    bitwise the `attentions` entry.  One launch per chosen layer (hip.attn_probs_grad), right where the hand-written backward holds d(ctx).
+    layers: indices into the layers of the pass, negative from the end (None: all); window: ((q_start, q_stop), (k_start, k_stop)) as
+    BertModel.forward's attn_window -- the rest of the (L, L) maps is never formed; want: "grad", "cam" or both;
+    grad_scale: the factor the differentiated score carries (a loss scale under fp16 operands): G is multiplied by 1 / grad_scale."""
+
+    def __init__(self, layers=None, window=None, want=("cam",), grad_scale=1.0):
+        self.layers = None if layers is None else tuple(int(l) for l in layers)
+        self.q_range, self.k_range = window if window is not None else (None, None)
+        self.want = (want,) if isinstance(want, str) else tuple(want)
+        if not self.want or len(set(self.want)) != len(self.want) or any(w not in ("grad", "cam") for w in self.want):
+            raise ValueError("AttnGradients: want=%r (one or both of 'grad', 'cam')" % (want,))
+        if self.layers is not None and not self.layers:
+            raise ValueError("AttnGradients: no layer chosen")
+        self.grad_scale = float(grad_scale)
+        if not self.grad_scale > 0 or not math.isfinite(self.grad_scale):
+            raise ValueError("AttnGradients: grad_scale=%r (a positive finite number)" % (grad_scale,))
+        self._pick, self._pending = (), None
+        self._grads, self._cams = {}, {}
+
+    def begin(self, n):
+        """A pass over n layers starts: resolve `layers` against it and forget what an earlier pass left."""
+        idx = range(n) if self.layers is None else self.layers
+        for i in idx:
+            if not -n <= i < n:
+                raise ValueError("AttnGradients: layer %d outside the %d layers of the pass" % (i, n))
+        self._pick = tuple(sorted(set(i % n for i in idx)))
+        self._pending = set(self._pick)
+        self._grads, self._cams = {}, {}
+
+    def wants(self, i):
+        return i in self._pick
+
+    def first(self):
+        return self._pick[0]
+
+    def add(self, i, qkv, dctx, lse, dims, key_bias):
+        if i not in self._pending:
+            return
+        B, L, H, scale = dims
+        res = hip.attn_probs_grad(qkv, dctx, lse, B, L, H, scale, key_bias, q_range=self.q_range, k_range=self.k_range, want=self.want,
+                                  grad_scale=1.0 / self.grad_scale)
+        for w, t in zip(self.want, res if isinstance(res, tuple) else (res,)):
+            (self._grads if w == "grad" else self._cams)[i] = t
+        self._pending.discard(i)
+
+    def _read(self, what, store):
+        if self._pending is None:
+            raise RuntimeError("AttnGradients.%s: the collector was not passed to a BertModel.forward(attn_grads=...) yet" % what)
+        if self._pending:
+            raise RuntimeError("AttnGradients.%s: backward() has not run through layers %s of the pass yet" % (what, sorted(self._pending)))
+        if what[:-1] not in self.want:
+            raise RuntimeError("AttnGradients.%s: the collector was built with want=%r" % (what, self.want))
+        return store
+
+    @property
+    def grads(self):
+        return self._read("grads", self._grads)
+
+    @property
+    def cams(self):
+        return self._read("cams", self._cams)
 
 
 class BertEncoder(nn.Module):
@@ -420,13 +519,20 @@ class BertModel(BertPreTrainedModel):
                                past_key_values=None, cross_attentions=None)
 
     def forward(self, input_ids=None, attention_mask=None, encoder_embeds=None, return_dict=True, mode='multi_modal', encoder_embeds_parts=None, out_rows=None,
-                output_attentions=None, output_hidden_states=None, attn_window=None, **unused):
+                output_attentions=None, output_hidden_states=None, attn_window=None, attn_grads=None, **unused):
         """output_attentions / output_hidden_states (xbert.py:953-954, None: the config's value): `attentions` = one (B, H, L, L) fp32 tensor per
         layer run, the softmax BEFORE dropout (hip.attn_probs on the layer's own qkv / lse / key bias); `hidden_states` = every layer's input
         and the final output, (B, L, D) fp32 ((len(out_rows), D) for the last one under out_rows).  Both are detached copies -- unlike the
         reference's they carry no autograd graph -- and asking for them changes no other result, gradient or dropout draw.
         attn_window (this repo's extension): ((q_start, q_stop), (k_start, k_stop)) -- each `attentions` entry is that window of the map only,
         (B, H, nq, nk); the rest is never computed (alpro_amd.grounding).
+        attn_grads (this repo's extension; the reference: .retain_grad() on `attentions`, or the save_attention hook of xbert.py:325-327): an
+        AttnGradients collector -- when the caller's backward() runs through this pass, the chosen layers leave d(score) / d(attention
+        probabilities) and / or the Grad-CAM map P * relu(dP) in it.  The pass then takes the anchored path even with every parameter frozen, and
+        the frozen prefix is shortened so that every chosen layer is inside the backward; grad mode off, or neither a trainable parameter nor an
+        input that requires a gradient, is refused (no backward would ever reach the layers).  Every output, gradient and dropout draw keeps its
+        bits.  None (the default): no object, no launch, no allocation.  With precise [CLS] rows the [CLS] query row of a text-layer map is the
+        16-bit graph's, as for `attentions`.
         encoder_embeds_parts (this repo's extension; the reference passes encoder_embeds): (text_pool (Pt, Lt, D), video_pool (Pv, Lv, D), ti (S,),
         vi (S,)) -- the fusion batch as a gather, sequence s = [text_pool[ti[s]] ; video_pool[vi[s]]], i.e. what the reference's
         torch.cat([text_embeds, video_embeds], dim=1) over concatenated / index-selected batches holds (alpro_models.py:278-281,325-330,360-363),
@@ -437,7 +543,9 @@ class BertModel(BertPreTrainedModel):
         want_att, want_hid = self.output_flags(output_attentions, output_hidden_states)
         tap = _AttnTap(attn_window) if want_att else None       # (both None with the flags off: no launch, no allocation)
         hidden = [] if want_hid else None
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+        if attn_grads is not None and not torch.is_grad_enabled():
+            raise RuntimeError("BertModel.forward(attn_grads=...): grad mode is off (torch.no_grad / inference_mode) -- no backward will run, the collector would stay empty")
+        if attn_grads is not None or (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())):
             lo, hi = self.encoder.layer_range(mode)
             params = [p for i in range(lo, hi) for p in self.encoder.layer[i].parameters()]
             if encoder_embeds is None and parts is None:
@@ -445,6 +553,14 @@ class BertModel(BertPreTrainedModel):
             run = _BertRun(self, input_ids, attention_mask, mode)
             run.out_rows = out_rows
             run.tap, run.hidden = tap, hidden
+            if attn_grads is not None:
+                acts = [parts[0], parts[1]] if parts is not None else [encoder_embeds]
+                if not any(p.requires_grad for p in params) and not any(torch.is_tensor(a) and a.requires_grad for a in acts):
+                    raise RuntimeError("BertModel.forward(attn_grads=...): nothing to differentiate -- no parameter of the pass is trainable and no input "
+                                       "requires a gradient, so the pass has no autograd node and no backward would reach it (pass encoder_embeds that "
+                                       "require a gradient, e.g. embeds.detach().requires_grad_())")
+                attn_grads.begin(hi - lo)
+                run.grads = attn_grads
             if parts is not None:
                 run.parts = (parts[2].contiguous(), parts[3].contiguous())
                 out = tr.run_anchored(run, [parts[0], parts[1]], params)
@@ -498,6 +614,7 @@ class _BertRun:
         self.parts = None   # (ti, vi): the input is a gather of (text pool, video pool) sequences, the two activations of forward()
         self.out_rows = None   # flat indices of the only output rows the caller reads (BertModel.forward out_rows)
         self.tap = self.hidden = None   # output_attentions / output_hidden_states: the collectors BertModel.forward reads after the pass
+        self.grads = None   # attn_grads: the AttnGradients collector the layers' backward fills
 
     def forward(self, encoder_embeds=None, video_pool=None):
         m, cfg = self.m, self.m.config
@@ -537,6 +654,12 @@ class _BertRun:
         stages = ([list(emb.parameters())] if self.from_ids else []) + [list(m.encoder.layer[i].parameters()) for i in range(lo, hi)]
         k = tr.frozen_prefix(stages, any(torch.is_tensor(a) and a.requires_grad for a in (encoder_embeds, video_pool)))
         first = lo + max(k - (1 if self.from_ids else 0), 0)
+        # a layer whose d(attention probabilities) somebody wants (attn_grads, or the save_attention flag) must be inside the backward range: the
+        # prefix ends in front of the first such layer (the frozen layers behind it then run their data-only backward)
+        watched = [i for i in range(lo, first) if m.encoder.layer[i].attention.self.save_attention]
+        if self.grads is not None:
+            watched.append(lo + self.grads.first())
+        first = min([first] + watched)
         self.range = (first, hi)
         self.prefix = k > 0
         for i in range(lo, hi):
@@ -546,7 +669,7 @@ class _BertRun:
             if i < first:
                 h32, h_t = m.encoder.layer[i](h32, h_t, kb, B, L, rows=rows, tap=self.tap)
                 continue
-            h32, h_t, sv = m.encoder.layer[i].forward_train(h32, h_t, kb, B, L, rows=rows, tap=self.tap)
+            h32, h_t, sv = m.encoder.layer[i].forward_train(h32, h_t, kb, B, L, rows=rows, tap=self.tap, attn_grads=self.grads, pass_index=i - lo)
             self.saved.append(sv)
         if self.hidden is not None:
             self.hidden.append(_hidden_copy(h32, B, L, self.out_rows))

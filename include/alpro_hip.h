@@ -633,6 +633,19 @@ int alpro_attn_probs(const void* qkv, const float* lse, const float* key_bias, f
  * no atomics, no workspace: bitwise reproducible. */
 int alpro_attn_temporal_probs(const void* qkv, const float* lse, float* out, int dtype, int64_t rows, int T, int H, float scale, void* stream);
 
+/* ---- gradient of a score w.r.t. the attention probabilities, and the Grad-CAM map (BertModel.forward attn_grads; the hook of xbert.py:325-327) ----
+ * For q0 <= q < q0 + nq, k0 <= k < k0 + nk, all fp32, (batch, H, nq, nk) contiguous:
+ *   grad_out[b][h][q - q0][k - k0] = grad_scale * <dctx[b*L + q][h*64 .. h*64 + 63], v_bhk>      (d score / d P, P the softmax BEFORE dropout)
+ *   cam_out [b][h][q - q0][k - k0] = P * max(grad, 0), P exactly alpro_attn_probs' value for the same qkv / lse / key_bias / scale
+ * qkv, lse, key_bias, L, the windows: as for alpro_attn_probs.  dctx (batch*L, H*64), dtype of qkv: the gradient w.r.t. the attention output,
+ * what alpro_attn_bwd takes as d_out.  grad_scale: one fp32 multiply on the 64-term dot product (the caller passes 1 / loss scale).  Either
+ * output may be NULL, not both; a NULL output costs nothing (without cam_out the scores are not formed and lse / key_bias are not read).
+ * No dropout arguments: the eval-mode gradient.  A masked key has P ~ 0 and grad whatever the dot product gives.  16-bit operands use the
+ * 16-bit MFMA, fp32 the fp32 MFMA (exact products).  qkv, dctx and both outputs 16-byte aligned.  Every argument is checked before the first
+ * HIP call.  One launch, no LDS, no atomics, no workspace: bitwise reproducible. */
+int alpro_attn_probs_grad(const void* qkv, const void* dctx, const float* lse, const float* key_bias, float* grad_out, float* cam_out, int dtype,
+                          int batch, int L, int H, float scale, float grad_scale, int q0, int nq, int k0, int nk, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
