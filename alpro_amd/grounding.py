@@ -7,6 +7,9 @@ hip.attn_probs is asked for the window (text rows) x (patch keys) of every map, 
 The fusion maps are collapsed over time (the fusion encoder sees temporally pooled patch tokens).  Where the visual encoder itself looks, and in
 which frame, is in the maps of its divided space-time blocks: frame_patch_attention returns the frame's [CLS] query row of the spatial maps
 (again a window: no (1+N, 1+N) map is formed), patch_temporal_attention the (T, T) temporal map of every patch position.
+
+At pixel resolution, per frame: pixel_gradient is d ITM score / d visual_inputs through the fusion layers, the visual encoder and the patch
+embedding; text_to_pixel_saliency reduces its channels (input gradient, gradient x input).
 """
 import math
 
@@ -82,12 +85,7 @@ def text_to_patch_gradcam(model, text_input_ids, text_input_mask, video_embeds, 
     hg = math.isqrt(Lv - 1) if Lv > 1 else 0
     if video_embeds.dim() != 3 or video_embeds.shape[0] != B or hg < 1 or hg * hg != Lv - 1:
         raise ValueError("%s: video_embeds %s is not (B=%d, 1 + Hg*Wg, D) with a square patch grid" % (what, tuple(video_embeds.shape), B))
-    if grad_scale is None:
-        from alpro_amd.amp import LossScaler
-        grad_scale = LossScaler()._init if rt.compute_dtype() == torch.float16 else 1.0
-    grad_scale = float(grad_scale)
-    if not grad_scale > 0 or math.frexp(grad_scale)[0] != 0.5:
-        raise ValueError("%s: grad_scale=%r is not a positive power of two (the rescale of the gradient must be exact)" % (what, grad_scale))
+    grad_scale = _power_of_two_scale(grad_scale, what)
     bert = getattr(model.text_encoder, "bert", model.text_encoder)    # BertForMaskedLM, or the bare BertModel of the QA model
     lo, hi = bert.encoder.layer_range("fusion")
     pick = _layer_indices(layers, hi - lo)
@@ -118,6 +116,83 @@ def text_to_patch_gradcam(model, text_input_ids, text_input_mask, video_embeds, 
         raise RuntimeError("%s: the map is not finite at grad_scale=%g -- the scaled backward left fp16's range; pass a smaller power of two as grad_scale"
                            % (what, grad_scale))
     return res
+
+
+def _power_of_two_scale(grad_scale, what):
+    from alpro_amd import config as rt
+    if grad_scale is None:
+        from alpro_amd.amp import LossScaler
+        grad_scale = LossScaler()._init if rt.compute_dtype() == torch.float16 else 1.0
+    grad_scale = float(grad_scale)
+    if not grad_scale > 0 or math.frexp(grad_scale)[0] != 0.5:
+        raise ValueError("%s: grad_scale=%r is not a positive power of two (the rescale of the gradient must be exact)" % (what, grad_scale))
+    return grad_scale
+
+
+def pixel_gradient(model, text_input_ids, text_input_mask, visual_inputs, target=1, grad_scale=None, _what="pixel_gradient"):
+    """d score / d visual_inputs at pixel resolution: model any AlproBaseModel with an itm_head, in eval mode; text_input_ids / text_input_mask
+    (B, Lt) and visual_inputs (B, T, C, H, W), as the models take them, on the device.  Returns (B, T, C, H, W) fp32, contiguous, with
+    score = itm_head(fusion [CLS])[:, target].sum() over the pairs (caption b, clip b) (target 1: "match").  Where text_to_patch_gradcam gives
+    one patch grid per caption token, averaged over the frames, this says which pixels of which frame made the caption match; it is what
+    gradient x input, SmoothGrad, integrated gradients and adversarial-robustness evaluations start from.
+    The text pass runs without grad; the visual pass and the fusion pass run with grad on a detached copy of the clip, and the hand-written
+    backward goes through the fusion layers, the twelve divided space-time blocks and the patch embedding (alpro_unpatchify) to the pixels.
+
+    The model is left untouched, exactly as by text_to_patch_gradcam: every parameter's requires_grad is False for the duration (no
+    weight-gradient launch, no .grad, no flat optimizer buffer is written) and restored afterwards; the call bumps train.BACKWARD_EPOCH.
+    grad_scale: the score is multiplied by it and the gradient divided by it afterwards; a positive power of two, so the rescale is exact.
+    None: the initial scale of alpro_amd.amp.LossScaler under fp16 (whose backward must be scaled), 1 under bf16 / fp32.  A non-finite result
+    raises (fp16: lower grad_scale); there is no retry."""
+    from alpro_amd import config as rt
+    from alpro_amd.modeling.alpro_models import _linear32
+    what = _what
+    if model.training:
+        raise RuntimeError("%s inspects a trained model: call model.eval() first (no dropout, no drop-path, no RNG draw)" % what)
+    _grid(visual_inputs, what)
+    if text_input_ids.dim() != 2 or text_input_ids.shape != text_input_mask.shape or text_input_ids.shape[0] != visual_inputs.shape[0]:
+        raise ValueError("%s: text_input_ids %s / text_input_mask %s are not (B=%d, Lt), one caption per clip of visual_inputs %s"
+                         % (what, tuple(text_input_ids.shape), tuple(text_input_mask.shape), visual_inputs.shape[0], tuple(visual_inputs.shape)))
+    grad_scale = _power_of_two_scale(grad_scale, what)
+    B = visual_inputs.shape[0]
+    flags = [(p, p.requires_grad) for p in model.parameters()]
+    try:
+        for p, _ in flags:
+            p.requires_grad_(False)
+        with torch.no_grad():
+            text_embeds = model._text_embeds(text_input_ids, text_input_mask)
+        clip = visual_inputs.detach().float().clone().requires_grad_(True)
+        with torch.enable_grad():
+            video = model.visual_encoder.forward_features(clip.transpose(1, 2), return_all_tokens=True)
+            video_atts = torch.ones((B, video.shape[1]), dtype=text_input_mask.dtype, device=text_input_mask.device)
+            out = model._fusion(torch.cat([text_embeds, video.to(text_embeds.dtype)], dim=1), torch.cat([text_input_mask, video_atts], dim=1))
+            score = _linear32(out[:, 0, :], model.itm_head)[:, int(target)].sum() * grad_scale
+            with rt.loss_scaling(clip):   # (marks the backward as scaled: config.check_backward_precision)
+                score.backward()
+    finally:
+        for p, f in flags:
+            p.requires_grad_(f)
+    res = clip.grad
+    if grad_scale != 1.0:
+        res = res / grad_scale
+    if not bool(torch.isfinite(res).all()):
+        raise RuntimeError("%s: the gradient is not finite at grad_scale=%g -- the scaled backward left fp16's range; pass a smaller power of two as grad_scale"
+                           % (what, grad_scale))
+    return res
+
+
+SALIENCY_METHODS = ("grad_x_input", "grad")
+
+
+def text_to_pixel_saliency(model, text_input_ids, text_input_mask, visual_inputs, target=1, grad_scale=None, method="grad_x_input"):
+    """Pixel saliency of the ITM score: arguments as pixel_gradient; returns (B, T, H, W) fp32, the channels of g = pixel_gradient(...) reduced by
+    `method`: "grad" -> max_c |g| (input-gradient saliency), "grad_x_input" -> sum_c g * x (gradient x input, signed: the first-order share of
+    each pixel in the score)."""
+    if method not in SALIENCY_METHODS:
+        raise ValueError("text_to_pixel_saliency: method=%r (one of %s)" % (method, ", ".join(repr(m) for m in SALIENCY_METHODS)))
+    g = pixel_gradient(model, text_input_ids, text_input_mask, visual_inputs, target=target, grad_scale=grad_scale, _what="text_to_pixel_saliency")
+    if method == "grad":
+        return g.abs().amax(dim=2)
+    return (g * visual_inputs.detach().float()).sum(dim=2)
 
 
 def _visual_encoder(encoder, what):

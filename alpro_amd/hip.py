@@ -32,7 +32,7 @@ EXPORTS = ["alpro_hip_last_error", "alpro_hip_abi_version", "alpro_hip_set_optio
            "alpro_hip_sched_workspace_bytes", "alpro_hip_set_sched_workspace", "alpro_hip_release_stream", "alpro_gemm_qkv_tattn", "alpro_add_layernorm_pre_mlp2", "alpro_adamw_step_lp",
            "alpro_gemm_rows_f32_relu_mask", "alpro_clip_pool", "alpro_adamw_step_groups", "alpro_attn_temporal_fwd_drop", "alpro_attn_temporal_bwd_drop",
            "alpro_vit_final_pool_mode", "alpro_vit_final_pool_mode_bwd", "alpro_augment_stage", "alpro_augment_stats", "alpro_resized_crop",
-           "alpro_sim_topk", "alpro_sim_topk_workspace_bytes", "alpro_attn_probs", "alpro_attn_temporal_probs", "alpro_attn_probs_grad"]
+           "alpro_sim_topk", "alpro_sim_topk_workspace_bytes", "alpro_attn_probs", "alpro_attn_temporal_probs", "alpro_attn_probs_grad", "alpro_unpatchify"]
 
 
 class GemmDesc(ctypes.Structure):
@@ -165,6 +165,7 @@ def load():
     lib.alpro_attn_probs.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, i32, i32, i32, vp]
     lib.alpro_attn_temporal_probs.argtypes = [vp, vp, vp, i32, i64, i32, i32, f32, vp]
     lib.alpro_attn_probs_grad.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, i32, i32, i32, i32, vp]
+    lib.alpro_unpatchify.argtypes = [vp, i32, vp, i32, i32, i32, i32, vp]
     if lib.alpro_hip_abi_version() != ABI_VERSION:
         raise RuntimeError("libalpro_hip.so ABI version mismatch")
     _lib = lib
@@ -871,6 +872,28 @@ def patchify(img, dtype):
     BT, C, Hh, Ww = img.shape
     out = torch.empty((BT * (Hh // 16) * (Ww // 16), C * 256), dtype=dtype, device=img.device)
     _check(lib.alpro_patchify(_ptr(img), _ptr(out), _CODE[dtype], BT, C, Hh, Ww, _stream()), "alpro_patchify")
+    return out
+
+
+def unpatchify(rows, BT, C, H, W, out=None):
+    """The inverse of patchify (alpro_unpatchify): rows (BT * (H/16) * (W/16), C*256) in fp32, fp16 or bf16 -> (BT, C, H, W) fp32, every pixel
+    the widened value of one row element.  out: a contiguous fp32 tensor of BT*C*H*W elements to write into (any shape, e.g. a (B, T, C, H, W)
+    buffer); default a fresh (BT, C, H, W) one."""
+    lib = load()
+    _dev(rows)
+    if rows.dtype not in _CODE:
+        raise RuntimeError("unpatchify: rows must be fp32, fp16 or bf16 (got %s)" % rows.dtype)
+    if H <= 0 or W <= 0 or H % 16 or W % 16:
+        raise ValueError("unpatchify: image %dx%d not a multiple of the 16x16 patch" % (H, W))
+    if not rows.is_contiguous() or rows.dim() != 2 or tuple(rows.shape) != (BT * (H // 16) * (W // 16), C * 256):
+        raise ValueError("unpatchify: rows %s, expected a contiguous (%d, %d) for BT=%d C=%d image %dx%d" % (tuple(rows.shape), BT * (H // 16) * (W // 16), C * 256, BT, C, H, W))
+    if out is None:
+        out = torch.empty((BT, C, H, W), dtype=torch.float32, device=rows.device)
+    else:
+        _dev(out, torch.float32)
+        if not out.is_contiguous() or out.numel() != BT * C * H * W or out.device != rows.device:
+            raise ValueError("unpatchify: out must be a contiguous fp32 tensor of %d elements on %s" % (BT * C * H * W, rows.device))
+    _check(lib.alpro_unpatchify(_ptr(rows), _CODE[rows.dtype], _ptr(out), BT, C, H, W, _stream()), "alpro_unpatchify")
     return out
 
 

@@ -1019,13 +1019,21 @@ class VisionTransformer(nn.Module):
             tidx = nearest_index(self.time_embed.size(1), T, dev)
         return pidx, tidx
 
-    def _embed_backward(self, rows, dtok, B, T, N, Wg=None):
-        """Gradients of patch_embed.proj / cls_token / pos_embed / time_embed from dtok (B, 1+N*T, D)."""
+    def _embed_backward(self, rows, dtok, B, T, N, Wg=None, pixel_grad=False):
+        """Gradients of patch_embed.proj / cls_token / pos_embed / time_embed from dtok (B, 1+N*T, D).
+        pixel_grad (needs Wg): also the data gradient of the patch embedding, returned as a (B, T, C, H, W) fp32 tensor -- drows @ W through the
+        W^T operand of tr.transposed_operand, then alpro_unpatchify.  The CLS row, the tables and the conv bias are additive: nothing of them in it."""
         dt = rows.dtype
         D = self.embed_dim
         pe = self.patch_embed.proj
-        if tr.trainable(pe.weight):   # (frozen: neither the operand rows nor the GEMM)
+        dpix = None
+        if tr.trainable(pe.weight) or pixel_grad:   # (neither: no operand rows and no GEMM)
             drows = hip.gather_cast(dtok, dt, rows=B * T * N, map_mode=hip.MAP_PATCH_EMBED, map_p0=T, map_p1=N)
+        if pixel_grad:
+            C, Hh, Ww = pe.weight.shape[1], (N // Wg) * 16, Wg * 16
+            dpix = torch.empty((B, T, C, Hh, Ww), dtype=torch.float32, device=dtok.device)
+            hip.unpatchify(tr.dgrad(drows, tr.transposed_operand(self._ops, "patch_w^T", pe.weight, dt), out_dtype=torch.float32), B * T, C, Hh, Ww, out=dpix)
+        if tr.trainable(pe.weight):
             if dt != torch.float32:  # 16-bit operands: in-place TN weight gradient (contraction over the B*T*N patch rows)
                 gw = tr.grad_buffer(pe.weight, zero=True)[0]
                 hip.gemm_tn_acc(drows, rows, gw.view(D, -1))
@@ -1051,6 +1059,7 @@ class VisionTransformer(nn.Module):
             if tidx is not None:
                 dtime = torch.zeros((self.time_embed.size(1), D), dtype=dtime.dtype, device=dtime.device).index_put_((tidx,), dtime, accumulate=True)
             tr.add_grad(self.time_embed, dtime)
+        return dpix
 
     def stage_params(self):
         """Parameter lists of the encoder's stages in forward order -- embedding, block 0, block 1, ... -- for tr.frozen_prefix."""
@@ -1151,7 +1160,7 @@ class TimeSformer(nn.Module):
                                                                                                                self.num_frames, self.img_size, self.num_frames, G, G))
         m = self.model
         collect = _collector(len(m.blocks), output_attentions, output_hidden_states, attn_layers, attn_window)
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+        if torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters()) or x.requires_grad):   # (x.requires_grad: the pixel gradient)
             out = tr.run_anchored(_VisualRun(self, mode, collect), [x], list(self.parameters()))
             return out if collect is None else collect.result(out)
         B = x.shape[0]
@@ -1212,8 +1221,11 @@ class _VisualRun:
         m = self.enc.model
         B = x.shape[0]
         # the frozen prefix (requires_grad is read NOW, at every forward): k leading stages -- embedding, block 0, ... -- hold no trainable parameter
-        # and pixels need no gradient here, so those blocks run their no-grad forward and the backward ends at the input of block k - 1
-        k = tr.frozen_prefix(m.stage_params(), torch.is_tensor(x) and x.requires_grad)
+        # and pixels need no gradient, so those blocks run their no-grad forward and the backward ends at the input of block k - 1.  A clip that
+        # requires a gradient makes the prefix 0: the patch rows and the embedding stage are kept behind frozen parameters too, and backward()
+        # goes on through the patch embedding to the pixels
+        self.x_grad = (tuple(x.shape), x.dtype) if torch.is_tensor(x) and x.requires_grad else None
+        k = tr.frozen_prefix(m.stage_params(), self.x_grad is not None)
         self.nfro, self.embed_frozen = max(k - 1, 0), k >= 1
         tok, T, W, N = m._embed(x)
         collect, self.collect = self.collect, None   # (nothing of it is needed in backward)
@@ -1279,8 +1291,7 @@ class _VisualRun:
                                             emit=dict(dtype=emit_dt, scale=last["drop_m"], group=S_) if last is not None else None)
             dtok, dz = r if last is not None else (r, None)
         if last is None:
-            self.saved = self.rows = self.tok = None
-            return None
+            return self._embed_backward(dtok)
         bank = m.blocks[0]._bank()
         dt_run = last["dt"]
         banked = bank is not None and dt_run != torch.float32 and all(sv["merged"] for sv in self.saved)
@@ -1323,7 +1334,17 @@ class _VisualRun:
             sv.clear()
             if self.recompute:
                 marks[j] = rt.wgrad_side_event(dtok.device)
+        return self._embed_backward(dtok)
+
+    def _embed_backward(self, dtok):
+        """The embedding stage's backward behind the last block's, and the gradient of the clip when it asked for one: (B, C, T, H, W) in the
+        clip's dtype, a view of (B, T, C, H, W)-contiguous memory -- the models pass visual_inputs.transpose(1, 2), whose backward then hands
+        visual_inputs.grad over contiguous, without a copy."""
+        B, T, N = self.dims
+        dx = None
         if not self.embed_frozen:
-            m._embed_backward(self.rows, dtok, B, T, N, self.Wg)
+            dx = self.enc.model._embed_backward(self.rows, dtok, B, T, N, self.Wg, pixel_grad=self.x_grad is not None)
         self.saved = self.rows = self.tok = None
-        return None  # pixels need no gradient
+        if dx is None:
+            return None   # pixels need no gradient
+        return dx.to(self.x_grad[1]).transpose(1, 2)

@@ -545,7 +545,10 @@ class BertModel(BertPreTrainedModel):
         hidden = [] if want_hid else None
         if attn_grads is not None and not torch.is_grad_enabled():
             raise RuntimeError("BertModel.forward(attn_grads=...): grad mode is off (torch.no_grad / inference_mode) -- no backward will run, the collector would stay empty")
-        if attn_grads is not None or (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())):
+        # (an input that requires a gradient anchors the pass behind wholly frozen parameters too -- the data-only backward, e.g. towards the video
+        # pixels through the fusion layers: grounding.pixel_gradient; before, the graph ended here without a word)
+        acts_need_grad = any(torch.is_tensor(a) and a.requires_grad for a in ((parts[0], parts[1]) if parts is not None else (encoder_embeds,)))
+        if attn_grads is not None or (torch.is_grad_enabled() and (acts_need_grad or any(p.requires_grad for p in self.parameters()))):
             lo, hi = self.encoder.layer_range(mode)
             params = [p for i in range(lo, hi) for p in self.encoder.layer[i].parameters()]
             if encoder_embeds is None and parts is None:

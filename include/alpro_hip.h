@@ -275,6 +275,11 @@ int alpro_attn_fwd(const void* qkv, void* out, int dtype, int batch, int L, int 
 /* out[(b*T+t)*N + n, c*256 + i*16 + j] = img[b, t, c, ph*16 + i, pw*16 + j], n = ph*(W/16) + pw:
  * the im2col rows of the stride-16 Conv2d (vit.py:230-238), cast to `dtype`. */
 int alpro_patchify(const float* img, void* out, int dtype, int BT, int C, int Himg, int Wimg, void* stream);
+/* The inverse data movement (still ABI 22: an addition): img[bt, c, ph*16 + i, pw*16 + j] = (float) rows[bt*N + n, c*256 + i*16 + j].  rows in
+ * `dtype` (fp32, fp16 or bf16), img (BT, C, Himg, Wimg) fp32, both 16-byte aligned.  Every image element is written exactly once, as the widened
+ * value of one source element: no arithmetic, no atomics, no workspace, bitwise reproducible.  It ends the pixel gradient of the patch
+ * embedding (drows @ W -> image).  Every argument is checked before the first HIP call. */
+int alpro_unpatchify(const void* rows, int dtype, float* img, int BT, int C, int Himg, int Wimg, void* stream);
 
 /* Clip preparation in one pass over the raw pixels: ImageNorm (src/datasets/data_utils.py:437-457, applied to the three clip tensors at
  * dataloader.py:104-115) fused with the MPM random-erase crop (dataset_pretrain_sparse.py:277-311).  raw (B, T, 3, H, W) uint8 or fp32;
