@@ -656,23 +656,33 @@ def _window(r, L):
     return lo, hi - lo
 
 
+def _need_dev(fn, *named, optional=()):
+    """Every (name, tensor) pair must be a device tensor; `optional` pairs may be None."""
+    for name, t in named + tuple(o for o in optional if o[1] is not None):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError("%s: %s must be a device tensor (got %s): the hot path has no CPU fallback" % (fn, name, getattr(t, "device", type(t))))
+
+
+def _probs_args(fn, qkv, lse, key_bias, batch, L, H):
+    """The qkv / lse / key_bias shape checks attn_probs and attn_probs_grad share (fn: the caller, for the messages)."""
+    if qkv.dtype not in _CODE or qkv.dim() != 2 or tuple(qkv.shape) != (batch * L, 3 * H * 64) or not qkv.is_contiguous():
+        raise RuntimeError("%s: qkv must be a contiguous (batch*L, 3*H*64) = (%d, %d) fp32 / bf16 / fp16 tensor (got %s %s, strides %s)"
+                           % (fn, batch * L, 3 * H * 64, qkv.dtype, tuple(qkv.shape), tuple(qkv.stride())))
+    if lse.dtype != torch.float32 or tuple(lse.shape) != (batch, H, L) or not lse.is_contiguous():
+        raise RuntimeError("%s: lse must be a contiguous (batch, H, L) = (%d, %d, %d) fp32 tensor (got %s %s)" % (fn, batch, H, L, lse.dtype, tuple(lse.shape)))
+    if key_bias is not None and (key_bias.dtype != torch.float32 or tuple(key_bias.shape) != (batch, L) or not key_bias.is_contiguous()):
+        raise RuntimeError("%s: key_bias must be a contiguous (batch, L) = (%d, %d) fp32 tensor (got %s %s)" % (fn, batch, L, key_bias.dtype, tuple(key_bias.shape)))
+
+
 def attn_probs(qkv, lse, batch, L, H, scale, key_bias=None, q_range=None, k_range=None):
     """The softmax probabilities attn() never materialises (alpro_attn_probs): qkv (batch*L, 3*H*64) as the qkv GEMM wrote it, lse (batch, H, L)
     fp32 from attn(..., want_lse=True) on the same qkv / scale / key_bias -> (batch, H, nq, nk) fp32, the window q_range = (q_start, q_stop),
     k_range = (k_start, k_stop) of every (L, L) map (None: all rows / all keys).  Normalised over all L keys (a window is a slice, not a
     renormalised map); the probabilities before dropout."""
-    for name, t in (("qkv", qkv), ("lse", lse)) + ((("key_bias", key_bias),) if key_bias is not None else ()):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise RuntimeError("attn_probs: %s must be a device tensor (got %s): the hot path has no CPU fallback" % (name, getattr(t, "device", type(t))))
+    _need_dev("attn_probs", ("qkv", qkv), ("lse", lse), optional=(("key_bias", key_bias),))
     lib = load()
     batch, L, H = int(batch), int(L), int(H)
-    if qkv.dtype not in _CODE or qkv.dim() != 2 or tuple(qkv.shape) != (batch * L, 3 * H * 64) or not qkv.is_contiguous():
-        raise RuntimeError("attn_probs: qkv must be a contiguous (batch*L, 3*H*64) = (%d, %d) fp32 / bf16 / fp16 tensor (got %s %s, strides %s)"
-                           % (batch * L, 3 * H * 64, qkv.dtype, tuple(qkv.shape), tuple(qkv.stride())))
-    if lse.dtype != torch.float32 or tuple(lse.shape) != (batch, H, L) or not lse.is_contiguous():
-        raise RuntimeError("attn_probs: lse must be a contiguous (batch, H, L) = (%d, %d, %d) fp32 tensor (got %s %s)" % (batch, H, L, lse.dtype, tuple(lse.shape)))
-    if key_bias is not None and (key_bias.dtype != torch.float32 or tuple(key_bias.shape) != (batch, L) or not key_bias.is_contiguous()):
-        raise RuntimeError("attn_probs: key_bias must be a contiguous (batch, L) = (%d, %d) fp32 tensor (got %s %s)" % (batch, L, key_bias.dtype, tuple(key_bias.shape)))
+    _probs_args("attn_probs", qkv, lse, key_bias, batch, L, H)
     (q0, nq), (k0, nk) = _window(q_range, L), _window(k_range, L)
     # (the library refuses a window outside 0..L or an empty one; max(.., 0): such a call never allocates a negative size)
     out = torch.empty((batch, H, max(nq, 0), max(nk, 0)), dtype=torch.float32, device=qkv.device)
@@ -690,24 +700,15 @@ def attn_probs_grad(qkv, dctx, lse, batch, L, H, scale, key_bias=None, q_range=N
     want = (want,) if isinstance(want, str) else tuple(want)
     if not want or len(set(want)) != len(want) or any(w not in ("grad", "cam") for w in want):
         raise RuntimeError("attn_probs_grad: want=%r (one or both of 'grad', 'cam', each once)" % (want,))
-    for name, t in (("qkv", qkv), ("dctx", dctx), ("lse", lse)) + ((("key_bias", key_bias),) if key_bias is not None else ()):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise RuntimeError("attn_probs_grad: %s must be a device tensor (got %s): the hot path has no CPU fallback" % (name, getattr(t, "device", type(t))))
+    _need_dev("attn_probs_grad", ("qkv", qkv), ("dctx", dctx), ("lse", lse), optional=(("key_bias", key_bias),))
     lib = load()
     batch, L, H = int(batch), int(L), int(H)
-    if qkv.dtype not in _CODE or qkv.dim() != 2 or tuple(qkv.shape) != (batch * L, 3 * H * 64) or not qkv.is_contiguous():
-        raise RuntimeError("attn_probs_grad: qkv must be a contiguous (batch*L, 3*H*64) = (%d, %d) fp32 / bf16 / fp16 tensor (got %s %s, strides %s)"
-                           % (batch * L, 3 * H * 64, qkv.dtype, tuple(qkv.shape), tuple(qkv.stride())))
+    _probs_args("attn_probs_grad", qkv, lse, key_bias, batch, L, H)
     if dctx.dtype != qkv.dtype or tuple(dctx.shape) != (batch * L, H * 64) or not dctx.is_contiguous():
         raise RuntimeError("attn_probs_grad: dctx must be a contiguous (batch*L, H*64) = (%d, %d) %s tensor, the dtype of qkv (got %s %s, strides %s)"
                            % (batch * L, H * 64, qkv.dtype, dctx.dtype, tuple(dctx.shape), tuple(dctx.stride())))
-    if lse.dtype != torch.float32 or tuple(lse.shape) != (batch, H, L) or not lse.is_contiguous():
-        raise RuntimeError("attn_probs_grad: lse must be a contiguous (batch, H, L) = (%d, %d, %d) fp32 tensor (got %s %s)" % (batch, H, L, lse.dtype, tuple(lse.shape)))
-    if key_bias is not None and (key_bias.dtype != torch.float32 or tuple(key_bias.shape) != (batch, L) or not key_bias.is_contiguous()):
-        raise RuntimeError("attn_probs_grad: key_bias must be a contiguous (batch, L) = (%d, %d) fp32 tensor (got %s %s)" % (batch, L, key_bias.dtype, tuple(key_bias.shape)))
     (q0, nq), (k0, nk) = _window(q_range, L), _window(k_range, L)
-    # (the library refuses a window outside 0..L or an empty one; max(.., 0): such a call never allocates a negative size)
-    outs = {w: torch.empty((batch, H, max(nq, 0), max(nk, 0)), dtype=torch.float32, device=qkv.device) for w in want}
+    outs = {w: torch.empty((batch, H, max(nq, 0), max(nk, 0)), dtype=torch.float32, device=qkv.device) for w in want}   # (max(.., 0): as in attn_probs)
     _check(lib.alpro_attn_probs_grad(_ptr(qkv), _ptr(dctx), _ptr(lse), _ptr(key_bias), _ptr(outs.get("grad")), _ptr(outs.get("cam")), _CODE[qkv.dtype],
                                      batch, L, H, float(scale), float(grad_scale), q0, nq, k0, nk, _stream()), "alpro_attn_probs_grad")
     res = tuple(outs[w] for w in want)
@@ -718,9 +719,7 @@ def attn_temporal_probs(qkv, lse, T, H, scale):
     """The softmax probabilities attn_temporal() / gemm_qkv_tattn() never materialise (alpro_attn_temporal_probs): qkv (rows, 3*H*64) as the temporal
     qkv Linear wrote it, lse ((rows + 31) // 32, H, 32) fp32 from attn_temporal(..., want_lse=True) or gemm_qkv_tattn(..., want_qkv=True) on the same
     rows / scale -> (rows // T, H, T, T) fp32: group g is the rows g*T .. g*T + T - 1.  The probabilities before dropout."""
-    for name, t in (("qkv", qkv), ("lse", lse)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise RuntimeError("attn_temporal_probs: %s must be a device tensor (got %s): the hot path has no CPU fallback" % (name, getattr(t, "device", type(t))))
+    _need_dev("attn_temporal_probs", ("qkv", qkv), ("lse", lse))
     lib = load()
     T, H = int(T), int(H)
     if qkv.dtype not in _CODE or qkv.dim() != 2 or qkv.shape[1] != 3 * H * 64 or not qkv.is_contiguous():

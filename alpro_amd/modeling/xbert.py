@@ -541,65 +541,35 @@ class BertModel(BertPreTrainedModel):
         the last layer's row-wise tail runs on them alone (BertLayer.forward_train)."""
         parts = encoder_embeds_parts
         want_att, want_hid = self.output_flags(output_attentions, output_hidden_states)
-        tap = _AttnTap(attn_window) if want_att else None       # (both None with the flags off: no launch, no allocation)
-        hidden = [] if want_hid else None
         if attn_grads is not None and not torch.is_grad_enabled():
             raise RuntimeError("BertModel.forward(attn_grads=...): grad mode is off (torch.no_grad / inference_mode) -- no backward will run, the collector would stay empty")
+        acts = [parts[0], parts[1]] if parts is not None else [encoder_embeds] if encoder_embeds is not None else []
         # (an input that requires a gradient anchors the pass behind wholly frozen parameters too -- the data-only backward, e.g. towards the video
         # pixels through the fusion layers: grounding.pixel_gradient; before, the graph ended here without a word)
-        acts_need_grad = any(torch.is_tensor(a) and a.requires_grad for a in ((parts[0], parts[1]) if parts is not None else (encoder_embeds,)))
-        if attn_grads is not None or (torch.is_grad_enabled() and (acts_need_grad or any(p.requires_grad for p in self.parameters()))):
+        acts_need_grad = any(torch.is_tensor(a) and a.requires_grad for a in acts)
+        anchored = attn_grads is not None or (torch.is_grad_enabled() and (acts_need_grad or any(p.requires_grad for p in self.parameters())))
+        run = _BertRun(self, input_ids, attention_mask, mode, anchored=anchored)
+        run.out_rows = out_rows
+        run.tap = _AttnTap(attn_window) if want_att else None       # (both None with the flags off: no launch, no allocation)
+        run.hidden = [] if want_hid else None
+        if parts is not None:
+            run.parts = (parts[2].contiguous(), parts[3].contiguous())
+        if not anchored:
+            out = run.forward(*acts)
+        else:
             lo, hi = self.encoder.layer_range(mode)
             params = [p for i in range(lo, hi) for p in self.encoder.layer[i].parameters()]
-            if encoder_embeds is None and parts is None:
+            if not acts:
                 params += list(self.embeddings.parameters())
-            run = _BertRun(self, input_ids, attention_mask, mode)
-            run.out_rows = out_rows
-            run.tap, run.hidden = tap, hidden
             if attn_grads is not None:
-                acts = [parts[0], parts[1]] if parts is not None else [encoder_embeds]
-                if not any(p.requires_grad for p in params) and not any(torch.is_tensor(a) and a.requires_grad for a in acts):
+                if not any(p.requires_grad for p in params) and not acts_need_grad:
                     raise RuntimeError("BertModel.forward(attn_grads=...): nothing to differentiate -- no parameter of the pass is trainable and no input "
                                        "requires a gradient, so the pass has no autograd node and no backward would reach it (pass encoder_embeds that "
                                        "require a gradient, e.g. embeds.detach().requires_grad_())")
                 attn_grads.begin(hi - lo)
                 run.grads = attn_grads
-            if parts is not None:
-                run.parts = (parts[2].contiguous(), parts[3].contiguous())
-                out = tr.run_anchored(run, [parts[0], parts[1]], params)
-            else:
-                out = tr.run_anchored(run, [encoder_embeds] if encoder_embeds is not None else [], params)
-            return self._result(out, tuple(hidden) if want_hid else None, tuple(tap.maps) if want_att else None, return_dict)
-        dt = rt.compute_dtype()
-        cfg = self.config
-        if parts is not None:
-            B, L = parts[2].numel(), parts[0].shape[1] + parts[1].shape[1]
-            h32, h_t = hip.gather_seq(parts[0].contiguous().float(), parts[1].contiguous().float(), parts[2].contiguous(), parts[3].contiguous(), dt)
-            if h_t is None:
-                h_t = h32
-        elif encoder_embeds is None:
-            B, L = input_ids.shape
-            emb = self.embeddings
-            ep = float(cfg.hidden_dropout_prob) if emb.training else 0.0
-            h32, h_t = hip.bert_embed(input_ids.contiguous(), emb.word_embeddings.weight, emb.position_embeddings.weight,
-                                      emb.token_type_embeddings.weight, emb.LayerNorm.weight, emb.LayerNorm.bias, cfg.layer_norm_eps, dt,
-                                      drop_p=ep, drop_seed=rt.next_dropout_seed() if ep > 0 else 0)
-        else:
-            B, L, Hd = encoder_embeds.shape
-            h32 = encoder_embeds.reshape(B * L, Hd).contiguous().float()
-            h_t = hip.cast(h32, dt)
-        if attention_mask is None:
-            attention_mask = torch.ones((B, L), device=h32.device)
-        kb = self.key_bias(attention_mask)
-        lo, hi = self.encoder.layer_range(mode)
-        for i in range(lo, hi):
-            if want_hid:
-                hidden.append(_hidden_copy(h32, B, L))
-            h32, h_t = self.encoder.layer[i](h32, h_t, kb, B, L, rows=out_rows if i == hi - 1 else None, tap=tap)
-        out = h32.view(B, L, -1) if out_rows is None else h32
-        if want_hid:
-            hidden.append(_hidden_copy(h32, B, L, out_rows))
-        return self._result(out, tuple(hidden) if want_hid else None, tuple(tap.maps) if want_att else None, return_dict)
+            out = tr.run_anchored(run, acts, params)
+        return self._result(out, tuple(run.hidden) if want_hid else None, tuple(run.tap.maps) if want_att else None, return_dict)
 
 
 def _hidden_copy(h32, B, L, out_rows=None):
@@ -612,8 +582,9 @@ def _hidden_copy(h32, B, L, out_rows=None):
 class _BertRun:
     """Forward/backward of one text-mode or fusion-mode pass of BertModel for tr.Anchor."""
 
-    def __init__(self, model, input_ids, attention_mask, mode):
+    def __init__(self, model, input_ids, attention_mask, mode, anchored=True):
         self.m, self.ids, self.mask, self.mode = model, input_ids, attention_mask, mode
+        self.anchored = anchored   # a backward may run (tr.run_anchored); False: BertModel.forward's no-grad pass -- every layer runs its no-grad forward, nothing is kept
         self.parts = None   # (ti, vi): the input is a gather of (text pool, video pool) sequences, the two activations of forward()
         self.out_rows = None   # flat indices of the only output rows the caller reads (BertModel.forward out_rows)
         self.tap = self.hidden = None   # output_attentions / output_hidden_states: the collectors BertModel.forward reads after the pass
@@ -636,35 +607,37 @@ class _BertRun:
             self.ids = self.ids.contiguous()
             word = emb.word_embeddings.weight
             ep = float(cfg.hidden_dropout_prob) if emb.training else 0.0
-            self.emb_drop = (ep, rt.next_dropout_seed() if ep > 0 else 0)
+            drop = (ep, rt.next_dropout_seed() if ep > 0 else 0)
+            self.emb_drop = drop if self.anchored else None
             # pre-LayerNorm sum is needed by the LN backward: recompute it there from the tables (cheap gather)
             h32, h_t = hip.bert_embed(self.ids, word, emb.position_embeddings.weight, emb.token_type_embeddings.weight,
-                                      emb.LayerNorm.weight, emb.LayerNorm.bias, cfg.layer_norm_eps, dt,
-                                      drop_p=self.emb_drop[0], drop_seed=self.emb_drop[1])
+                                      emb.LayerNorm.weight, emb.LayerNorm.bias, cfg.layer_norm_eps, dt, drop_p=drop[0], drop_seed=drop[1])
         else:
             B, L, Hd = encoder_embeds.shape
             h32 = encoder_embeds.reshape(B * L, Hd).contiguous().float()
             h_t = hip.cast(h32, dt)
         mask = self.mask if self.mask is not None else torch.ones((B, L), device=h32.device)
         kb = m.key_bias(mask)
-        self.dims = (B, L)
-        self.from_ids = encoder_embeds is None and self.parts is None
-        self.saved = []
         lo, hi = m.encoder.layer_range(self.mode)
-        # the frozen prefix (tr.frozen_prefix; requires_grad is read now): leading stages -- the embeddings when this pass starts from ids, then the
-        # layers -- without a trainable parameter, provided no input (the fusion pass's text / video embeddings) needs a gradient: they run their
-        # no-grad forward (same dropout draws, nothing saved) and the backward ends at the first trainable layer's input
-        stages = ([list(emb.parameters())] if self.from_ids else []) + [list(m.encoder.layer[i].parameters()) for i in range(lo, hi)]
-        k = tr.frozen_prefix(stages, any(torch.is_tensor(a) and a.requires_grad for a in (encoder_embeds, video_pool)))
-        first = lo + max(k - (1 if self.from_ids else 0), 0)
-        # a layer whose d(attention probabilities) somebody wants (attn_grads, or the save_attention flag) must be inside the backward range: the
-        # prefix ends in front of the first such layer (the frozen layers behind it then run their data-only backward)
-        watched = [i for i in range(lo, first) if m.encoder.layer[i].attention.self.save_attention]
-        if self.grads is not None:
-            watched.append(lo + self.grads.first())
-        first = min([first] + watched)
-        self.range = (first, hi)
-        self.prefix = k > 0
+        first = hi   # layers lo .. first - 1 run their no-grad forward; not anchored: that is all of them
+        if self.anchored:
+            self.dims = (B, L)
+            self.from_ids = encoder_embeds is None and self.parts is None
+            self.saved = []
+            # the frozen prefix (tr.frozen_prefix; requires_grad is read now): leading stages -- the embeddings when this pass starts from ids, then
+            # the layers -- without a trainable parameter, provided no input (the fusion pass's text / video embeddings) needs a gradient: they run
+            # their no-grad forward (same dropout draws, nothing saved) and the backward ends at the first trainable layer's input
+            stages = ([list(emb.parameters())] if self.from_ids else []) + [list(m.encoder.layer[i].parameters()) for i in range(lo, hi)]
+            k = tr.frozen_prefix(stages, any(torch.is_tensor(a) and a.requires_grad for a in (encoder_embeds, video_pool)))
+            first = lo + max(k - (1 if self.from_ids else 0), 0)
+            # a layer whose d(attention probabilities) somebody wants (attn_grads, or the save_attention flag) must be inside the backward range:
+            # the prefix ends in front of the first such layer (the frozen layers behind it then run their data-only backward)
+            watched = [i for i in range(lo, first) if m.encoder.layer[i].attention.self.save_attention]
+            if self.grads is not None:
+                watched.append(lo + self.grads.first())
+            first = min([first] + watched)
+            self.range = (first, hi)
+            self.prefix = k > 0
         for i in range(lo, hi):
             rows = self.out_rows if i == hi - 1 else None
             if self.hidden is not None:
