@@ -132,17 +132,29 @@ __device__ __forceinline__ float wave_max(float v) {
 
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 // 0.5 * erfc(z) for z >= 0 as ONE exponential: erfc(z) ~= 2^q(z), q a degree-5 polynomial without constant term fitted on
-// [0, 5.5] (max abs error 6.8e-7; beyond 5.5 the polynomial keeps falling and 2^q underflows to 0 like erfc does).
-// No reciprocal and no second transcendental: 5 FMA-class ops + v_exp_f32, vs rcp + exp + 7 for an Abramowitz-Stegun rational form.
+// [0, 5.5] (beyond 5.5 the polynomial keeps falling -- to -inf, never through a NaN, for every z up to +inf -- and 2^q underflows to 0 like
+// erfc does).  The polynomial alone reaches 3.41e-7 on Phi (6.8e-7 on erfc) at its last extremum, z = 2.47, where it is 0.14 % BELOW erfc,
+// and 0.5 - (0.5 - h) for a negative x adds up to 2^-26: tests/test_hip_gelu_range.py saw gelu(-3.5) outside 3.4e-7 |x|.  So the constant
+// term rises from -1 to -1 + 2^-12 (2^q grows by 0.017 %) over z in [2.3, 2.425], i.e. from |x| = 3.25, and stays there: the tail, where the
+// fit is too small throughout, moves towards erfc, and below z = 2.3 not one bit changes.  |Phi error| <= 3.1e-7 in exact arithmetic.
+// No reciprocal and no second transcendental: 5 FMA-class ops + v_exp_f32 (+ FMA and v_med3_f32 for the tail), vs rcp + exp + 7 for an
+// Abramowitz-Stegun rational form.
+constexpr float ERFC_TAIL_SLOPE = 0x1p-9f, ERFC_TAIL_OFFSET = -1.0f - 2.3f * 0x1p-9f, ERFC_TAIL_TOP = -1.0f + 0x1p-12f;
+__device__ __forceinline__ float erfc_tail_term(float z) {   // -1 for z <= 2.3 (and for a NaN z, which the next FMA passes on), the top from 2.425
+  return __builtin_amdgcn_fmed3f(fmaf(z, ERFC_TAIL_SLOPE, ERFC_TAIL_OFFSET), -1.0f, ERFC_TAIL_TOP);
+}
 __device__ __forceinline__ float half_erfc_pos(float z) {
   float q = fmaf(z, -0.00296695f, 0.02966973f);
   q = fmaf(z, q, -0.14875628f);
   q = fmaf(z, q, -0.91847146f);
   q = fmaf(z, q, -1.62789348f);
-  return __builtin_amdgcn_exp2f(fmaf(z, q, -1.0f));
+  return __builtin_amdgcn_exp2f(fmaf(z, q, erfc_tail_term(z)));
 }
-// exact-mode (f32 storage) keeps libm erff; 16-bit storage: gelu(x) = x * Phi(x), Phi(x) = 0.5 erfc(-x / sqrt 2),
-// |error| <= 1.2e-6 absolute (three orders below bf16 resolution at |x| ~ 1)
+// exact-mode (f32 storage) keeps libm erff; 16-bit storage: gelu(x) = x * Phi(x), Phi(x) = 0.5 erfc(-x / sqrt 2).
+// Accuracy, for EVERY finite x (tests/test_hip_gelu_range.py asserts it on every 16-bit input, a 2^-12 grid to +-16 and far values to 3e38):
+// |Phi error| <= E = 3.4e-7 plus 4 ulp of Phi (the fit's 3.1e-7 and its fp32 evaluation), so |gelu error| <= E |x| plus fp32 rounding -- NOT an
+// absolute bound: 1.5e-6 at x = 3.6, still three orders below bf16 resolution there -- and |gelu' error| <= E plus rounding.  Finite in, finite
+// out: beyond the fit's range h underflows to 0 and y = x or -0, dy = 1 or 0; NaN gives NaN.
 template <typename T> __device__ __forceinline__ float gelu_fast(float x) {
   if constexpr (sizeof(T) == 4) return gelu_erf(x);
   else {
@@ -166,12 +178,15 @@ template <typename T> __device__ __forceinline__ float gelu_grad(float x) {
 // gelu(x) and gelu'(x) for TWO elements with ONE exponential each (round 5).  Phi(-|x|) = 0.5 erfc(|x| / sqrt 2) = exp(-x^2 / 2) * g(|x|) with
 // g(t) = 0.5 erfcx(t / sqrt 2), and exp(-x^2 / 2) is what phi(x) needs anyway: g is smooth and slowly varying, a degree-9 polynomial in |x|
 // (weighted minimax fit, the weight being the exponential in front of it: |Phi error| <= 3.2e-7 in fp32 arithmetic on [0, 13], checked against
-// scipy's erfc in the fit script's output recorded in DESIGN.md) replaces the second v_exp_f32 of the round-3 form (erfc ~= 2^q(z) plus a
-// separate exp for phi).  Written on 2-vectors so that the nine Horner steps are v_pk_fma_f32 (two elements per issue slot): per pair of
+// scipy's erfc in the fit script's output recorded in DESIGN.md; so |gelu error| <= 3.2e-7 |x| plus rounding, and the form holds for every
+// finite x: see the first line of the function) replaces the second v_exp_f32 of the round-3 form (erfc ~= 2^q(z) plus a separate exp for phi).  Written on 2-vectors so that the nine Horner steps are v_pk_fma_f32 (two elements per issue slot): per pair of
 // elements 9 + ~10 VALU slots and 2 transcendentals, against 25 + 4.  The GELU-saving fc1 epilogue spent about 40 % of a tile's time here.
 typedef float f32x2v __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void gelu_and_grad2(f32x2v x, f32x2v& y, f32x2v& dy) {
-  const f32x2v t = {fabsf(x.x), fabsf(x.y)};
+  // The polynomial is evaluated at min(|x|, 13), the end of its fit: beyond it the leading -8.06e-6 t^9 keeps growing and overflows to -inf from
+  // |x| ~ 7.4e4, where e is 0 -- h = 0 * -inf was NaN for a finite input.  e still comes from x itself and is below 2^-121 there.  (v_min_f32
+  // takes |x| as a source modifier: the same two VALU slots as the two fabsf.  A NaN x leaves t = 13 and reaches y and dy through e.)
+  const f32x2v t = {fminf(fabsf(x.x), 13.0f), fminf(fabsf(x.y), 13.0f)};
   f32x2v p = t * (f32x2v){-8.062383613e-06f, -8.062383613e-06f} + (f32x2v){1.519315725e-04f, 1.519315725e-04f};
   p = p * t + (f32x2v){-1.271098853e-03f, -1.271098853e-03f};
   p = p * t + (f32x2v){6.382599637e-03f, 6.382599637e-03f};
@@ -196,7 +211,8 @@ __device__ __forceinline__ f32x2v gelu_fast2(f32x2v x) {
   q = z * q + (f32x2v){-0.14875628f, -0.14875628f};
   q = z * q + (f32x2v){-0.91847146f, -0.91847146f};
   q = z * q + (f32x2v){-1.62789348f, -1.62789348f};
-  q = z * q + (f32x2v){-1.0f, -1.0f};
+  const f32x2v r = z * (f32x2v){ERFC_TAIL_SLOPE, ERFC_TAIL_SLOPE} + (f32x2v){ERFC_TAIL_OFFSET, ERFC_TAIL_OFFSET};   // erfc_tail_term on two elements
+  q = z * q + (f32x2v){__builtin_amdgcn_fmed3f(r.x, -1.0f, ERFC_TAIL_TOP), __builtin_amdgcn_fmed3f(r.y, -1.0f, ERFC_TAIL_TOP)};
   const f32x2v h = {__builtin_amdgcn_exp2f(q.x), __builtin_amdgcn_exp2f(q.y)};
   const f32x2v cdf = {0.5f + copysignf(0.5f - h.x, x.x), 0.5f + copysignf(0.5f - h.y, x.y)};
   return x * cdf;

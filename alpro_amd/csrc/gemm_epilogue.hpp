@@ -62,7 +62,7 @@ __device__ __forceinline__ void wave_lds_order() { asm volatile("" ::: "memory")
 
 template <typename T, int ACT> __device__ __forceinline__ float apply_act(float x) {
   if (ACT == ALPRO_ACT_GELU) return gelu_fast<T>(x);   // (GELU_SAVE_GRAD computes gelu together with gelu' before this point)
-  if (ACT == ALPRO_ACT_RELU) return fmaxf(x, 0.f);
+  if (ACT == ALPRO_ACT_RELU) return x < 0.f ? 0.f : x;   // NaN passes, as torch.relu and alpro_gemm_rows_f32 (fmaxf turned it into 0)
   return x;
 }
 

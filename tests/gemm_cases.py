@@ -13,7 +13,8 @@ row m multiplies by A[m, 0] in [-3, 3] -- and an integer bias on top where the e
 every run that each case does exercise what it claims.
 
 The GELU family (GELU, GELU_SAVE_GRAD, GELU_BWD) is not exact: those cases keep exact pre-activations (alpha = 2^-j puts them inside
-[-6, 6]) and are compared under the tolerances tests/test_hip_ops.py already uses.
+[-6, 6]) and are compared under the tolerances tests/test_hip_ops.py already uses; what each GELU form is held to over every 16-bit input,
+the far tails and non-finite values is the subject of tests/gelu_cases.py.
 """
 import math
 import zlib
