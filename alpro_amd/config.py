@@ -1,7 +1,11 @@
 """Runtime knobs of the MI355X path (not part of the reference's JSON surface; all optional)."""
+import contextlib
 import os
+import weakref
 
 import torch
+
+from alpro_amd import streams
 
 _DTYPES = {"bf16": torch.bfloat16, "bfloat16": torch.bfloat16, "f16": torch.float16, "fp16": torch.float16,
            "float16": torch.float16, "f32": torch.float32, "fp32": torch.float32, "float32": torch.float32}
@@ -35,12 +39,62 @@ class use_compute_dtype:
         set_compute_dtype(self.prev)
 
 
+# ---- runtime switches: each is one _Switch in SWITCHES; the set_* / getter names below are its `set` and the switch itself
+_ON, _OFF = ("1", "true", "on"), ("0", "false", "off")
+SWITCHES = {}     # name (the * of set_*) -> _Switch
+
+
+class _Switch:
+    """With `decide` (value, *args) -> bool a tri-state switch: it holds a lower-case word (one of _ON, one of _OFF, or its third word, the default)
+    and calling it decides for the arguments.  Without: on / off, it holds a bool and calling it returns that."""
+
+    def __init__(self, name, env, default, decide=None, parse=None):
+        self.name, self.env, self.default, self.decide = name, env, default, decide
+        self.parse = parse or (str.lower if decide else lambda v: v != "0")
+        self.read_env()
+        SWITCHES[name] = self
+
+    def read_env(self):
+        self.value = self.parse(os.environ.get(self.env, self.default))
+
+    def set(self, v):
+        self.value = (v.lower() if isinstance(v, str) else ("1" if v else "0")) if self.decide else bool(v)
+
+    def __call__(self, *args, **kw):
+        return self.decide(self.value, *args, **kw) if self.decide else self.value
+
+    def __getitem__(self, i):   # switch[0]: the value it holds, which `set` takes back unchanged
+        return (self.value,)[i]
+
+    def __setitem__(self, i, v):   # switch[0] = a value read from switch[0] earlier
+        self.value = (v,)[i]
+
+
+@contextlib.contextmanager
+def override(*names, **values):
+    """`with override("cls_stream", split_streams="0", wgrad_stream=False): ...` -- sets the switches given by keyword as their set_* would and, on
+    exit, puts these and the ones merely named (for a block that calls their set_* itself) back to exactly what they held."""
+    prev = {n: SWITCHES[n].value for n in (*names, *values)}
+    try:
+        for n, v in values.items():
+            SWITCHES[n].set(v)
+        yield
+    finally:
+        for n, v in prev.items():
+            SWITCHES[n].value = v
+
+
+def _on_or_inference_only(v, training=False):
+    return v in _ON or (v == "infer" and not training)
+
+
 # ---- precise CLS rows (round 4).  The VTC features are projections of one row per sequence (the CLS token); in the 16-bit modes its own
 # chain of roundings (LayerNorm output -> q/k/v -> attention output -> projection -> MLP, once per block) carries most of the VTC-logit
 # error, and re-evaluating exactly those rows in fp32 costs < 1e-3 of the FLOPs (csrc/cls_precise.hip, DESIGN.md section 2).
 # ALPRO_CLS_PRECISE = auto (default: on with fp16 operands -- the mode that then meets "VTC logits within 1e-3" on every reference fixture;
 # off with bf16, whose 8-bit mantissa stays far from the bar either way) | 1 | 0.
-_cls_precise = [os.environ.get("ALPRO_CLS_PRECISE", "auto").lower()]
+_cls_precise = _Switch("cls_precise", "ALPRO_CLS_PRECISE", "auto", lambda v, dt: dt == torch.float16 if v == "auto" else v in _ON)
+set_cls_precise = _cls_precise.set
 _cls_off = [0]
 
 
@@ -48,9 +102,12 @@ def cls_precise(dt=None):
     dt = dt if dt is not None else _compute_dtype
     if dt == torch.float32 or _cls_off[0] > 0:
         return False
-    if _cls_precise[0] == "auto":
-        return dt == torch.float16
-    return _cls_precise[0] in ("1", "true", "on")
+    return _cls_precise(dt)
+
+
+def use_cls_precise(v):
+    """`with use_cls_precise(False): ...` (tests, bench.py's mode table)."""
+    return override(cls_precise=v)
 
 
 # The chain's launches are skinny (32 ... 512 rows against whole weight matrices: latency, not throughput).  On a second HIP stream, ordered
@@ -58,18 +115,8 @@ def cls_precise(dt=None):
 # (round 5; it rests on the dynamic tile scheduler: a persistent GEMM that finds a CU taken must not wait a round for it).  Measured
 # (profiles/r5_cls_stream_ab.txt): B = 32 encoder forward 18.48 -> 18.01 ms, training step unchanged (161.6 ms either way).
 # ALPRO_CLS_STREAM = infer (default: the inference forward only) | 1 (training forward too) | 0.
-_cls_stream = [os.environ.get("ALPRO_CLS_STREAM", "infer").lower()]
-
-
-def cls_stream(training=False):
-    v = _cls_stream[0]
-    if v in ("1", "true", "on"):
-        return True
-    return v == "infer" and not training
-
-
-def set_cls_stream(v):
-    _cls_stream[0] = v.lower() if isinstance(v, str) else ("1" if v else "0")
+cls_stream = _cls_stream = _Switch("cls_stream", "ALPRO_CLS_STREAM", "infer", _on_or_inference_only)    # cls_stream(training=False)
+set_cls_stream = cls_stream.set
 
 
 # Round 6: the temporal half's qkv Linear and its T-frame attention as ONE launch (alpro_gemm_qkv_tattn: q | k | v are consumed out of the GEMM's
@@ -78,44 +125,28 @@ def set_cls_stream(v):
 # for the backward) | 0 (the two launches everywhere).  Measured (MI355X, B = 64, fp16, one box): inference form 365 us against 308 + 115 us for
 # the two launches inside a step; training form 441 us against the same 423 us -- its 256 x 192 tiles run the K loop at ~975 TF/s where the
 # 8-phase qkv GEMM reaches ~1150, so with q | k | v still to be written the fusion does not pay in training and stays off there.
-_fuse_tattn = [os.environ.get("ALPRO_FUSE_TATTN", "infer").lower()]
-
-
-def fuse_temporal_attention(training=False):
-    v = _fuse_tattn[0]
-    if v in ("1", "true", "on"):
-        return True
-    return v == "infer" and not training
-
-
-def set_fuse_temporal_attention(v):
-    _fuse_tattn[0] = v.lower() if isinstance(v, str) else ("1" if v else "0")
+fuse_temporal_attention = _fuse_tattn = _Switch("fuse_temporal_attention", "ALPRO_FUSE_TATTN", "infer", _on_or_inference_only)    # fuse_temporal_attention(training=False)
+set_fuse_temporal_attention = fuse_temporal_attention.set
 
 
 # Round 6: the no-grad encoder forward as two half batches on two HIP streams (modeling/timesformer/vit.py::run_blocks).  Every big launch of a
 # block is a persistent kernel whose last round of tiles leaves most CUs idle (the N = 768 projections at B = 32: 591 tiles = 2.3 rounds on 256
 # CUs) and the next launch of the same stream depends on it; the other half's launches do not, and the dynamic tile scheduler lets their
 # workgroups start on the CUs the first kernel's workgroups have left.  ALPRO_SPLIT_STREAMS = 0 | 1 | auto (default; on for even B >= 16).
-_split_streams = [os.environ.get("ALPRO_SPLIT_STREAMS", "auto").lower()]
-
-
-def split_streams(B):
-    v = _split_streams[0]
-    if v in ("0", "false", "off") or B % 2 != 0:
+def _split_for(v, B):
+    if v in _OFF or B % 2 != 0:
         return False
-    if v in ("1", "true", "on"):
-        return B >= 2
-    return B >= 16
+    return B >= (2 if v in _ON else 16)
+
+
+split_streams = _split_streams = _Switch("split_streams", "ALPRO_SPLIT_STREAMS", "auto", _split_for)    # split_streams(B)
+set_split_streams = split_streams.set
 
 
 def split_lockstep():
     """ALPRO_SPLIT_LOCKSTEP=1: the two streams meet at every block boundary (measurement aid: a block's launches are then bracketed on the launch
     stream); default: they meet once, behind the last block."""
     return os.environ.get("ALPRO_SPLIT_LOCKSTEP", "0") == "1"
-
-
-def set_split_streams(v):
-    _split_streams[0] = v.lower() if isinstance(v, str) else ("1" if v else "0")
 
 
 # Round 6 (third session): weight gradients on a side stream.  Inside an anchored backward (alpro_amd.modeling.train.Anchor) every 16-bit weight-gradient
@@ -125,9 +156,9 @@ def set_split_streams(v):
 # forward buys: the weight-gradient kernel's workgroups take the CUs a persistent GEMM's last, partly filled round of tiles leaves idle, and vice
 # versa.  Sums are unchanged bit for bit (each kernel's own order; accumulations into one .grad stay ordered on the side stream).
 # Measured (profiles/r6_wgrad_side_stream_ab.txt): B = 64 pretrain step -0.3 ... -1.0 % on one box, +0.08 GB peak memory.  ALPRO_WGRAD_STREAM = 0 | 1 (default 1).
-_wgrad_stream = [os.environ.get("ALPRO_WGRAD_STREAM", "1") != "0"]
+wgrad_stream_enabled = _Switch("wgrad_stream", "ALPRO_WGRAD_STREAM", "1")
+set_wgrad_stream = wgrad_stream_enabled.set
 _wgrad_active = [0]      # > 0 while an anchored backward runs
-_WGRAD_SIDE = {}         # (device index, launch stream handle) -> [side stream, work pending]
 
 
 def _several_ranks():
@@ -143,62 +174,47 @@ def _several_ranks():
         return False
 
 
-def set_wgrad_stream(v):
-    _wgrad_stream[0] = bool(v)
-
-
-def wgrad_stream_enabled():
-    return _wgrad_stream[0]
+def _forks(switch, device, single_gpu_only=True):
+    """True if the role that `switch` governs takes a side stream on `device`: switched on, a GPU, and -- the single-GPU schedules, see
+    _several_ranks -- not in a job of several ranks unless the switch's environment variable says `force`."""
+    return switch.value and device.type == "cuda" and not (single_gpu_only and _several_ranks() and os.environ.get(switch.env) != "force")
 
 
 def wgrad_scope(enter):
+    """Entering / leaving an anchored backward; returns how many are running now."""
     _wgrad_active[0] += 1 if enter else -1
+    return _wgrad_active[0]
 
 
 def wgrad_side_stream(device):
     """The side stream of the current launch stream, or None when weight gradients stay on the launch stream."""
-    if not (_wgrad_stream[0] and _wgrad_active[0] > 0 and device.type == "cuda") or (_several_ranks() and os.environ.get("ALPRO_WGRAD_STREAM") != "force"):
+    if not (_wgrad_active[0] > 0 and _forks(wgrad_stream_enabled, device)):
         return None
-    import torch
     cur = torch.cuda.current_stream(device)
-    if any(s.cuda_stream == cur.cuda_stream for s in _TEXT_SIDE.values()):
+    if streams.TEXT.owns(cur):
         # a backward that already runs on the text side stream keeps its weight gradients there: at most four streams are active at a time (launch, text,
         # weight gradients in backward; launch, text, 2 x prompter in forward) -- the number of hardware queues that do not share a dispatch pipe
         # (profiles/r6_hw_queues.txt: a side stream of the side stream measured 148.75 ms against 148.5; default stream priority: high costs 14 %)
         return None
-    key = (device.index if device.index is not None else torch.cuda.current_device(), cur.cuda_stream)
-    ent = _WGRAD_SIDE.get(key)
-    if ent is None:
-        ent = _WGRAD_SIDE[key] = [torch.cuda.Stream(device), False]
-    ent[1] = True
-    return ent[0]
+    ent = streams.WGRAD.get(device, cur)
+    ent.pending = True
+    return ent.stream
 
 
 def side_streams_of_current(device):
     """Raw handles of the side streams that carry weight-gradient GEMMs for the current launch stream (created if the switch is on): per-stream
     launch options of the launch stream (FlatAdamW's cu_budget while all-reduces are in flight) have to be mirrored onto them -- the weight-gradient
     kernel plans one workgroup per available CU, and it runs on the side stream now."""
-    if not (_wgrad_stream[0] and device.type == "cuda") or (_several_ranks() and os.environ.get("ALPRO_WGRAD_STREAM") != "force"):
-        return []
-    import torch
-    key = (device.index if device.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(device).cuda_stream)
-    ent = _WGRAD_SIDE.get(key)
-    if ent is None:
-        ent = _WGRAD_SIDE[key] = [torch.cuda.Stream(device), False]
-    return [ent[0].cuda_stream]
+    return [streams.WGRAD.get(device).stream.cuda_stream] if _forks(wgrad_stream_enabled, device) else []
 
 
-def join_wgrad():
-    """The current stream of every device waits for the weight gradients that were launched from it."""
-    if not _WGRAD_SIDE:
-        return
-    import torch
-    for (idx, handle), ent in _WGRAD_SIDE.items():
-        if ent[1]:
-            cur = torch.cuda.current_stream(idx)
-            if cur.cuda_stream == handle:
-                cur.wait_stream(ent[0])
-                ent[1] = False
+def wgrad_side_event(device):
+    """An event behind every weight gradient launched so far on the side stream of the current launch stream, or None if there is none."""
+    ent = streams.WGRAD.peek(device)
+    return ent.stream.record_event() if (ent is not None and ent.pending) else None
+
+
+join_wgrad = streams.WGRAD.join     # the current stream of every device waits for the weight gradients that were launched from it
 
 
 # Round 6 (third session): the pretraining forward's 2B-caption text-encoder pass (M = 2B x 40 rows: 60 ... 240 tiles per Linear, a quarter to all of the
@@ -207,42 +223,16 @@ def join_wgrad():
 # (the VTC features); the side stream's parameter gradients are handed to the caller's stream by an end-of-backward callback, and any gradient range
 # reported final to the exchange (N > 1) waits for the side stream first.  Measured (profiles/r6_text_side_stream_ab.txt): B = 64 pretrain step
 # 151.7 -> 149.4 ms (-1.5 %, A/B/A/B on one box), outputs and gradients bit for bit, +0.14 GB.  ALPRO_TEXT_STREAM = 0 | 1 (default 1).
-_text_stream = [os.environ.get("ALPRO_TEXT_STREAM", "1") != "0"]
-_TEXT_SIDE = {}          # (device index, launch stream handle) -> side stream
-
-
-def set_text_stream(v):
-    _text_stream[0] = bool(v)
-
-
-def text_stream_enabled():
-    return _text_stream[0]
+text_stream_enabled = _Switch("text_stream", "ALPRO_TEXT_STREAM", "1")
+set_text_stream = text_stream_enabled.set
 
 
 def text_side_stream(device):
-    if not (_text_stream[0] and device.type == "cuda"):
-        return None
-    import torch
-    key = (device.index if device.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(device).cuda_stream)
-    s = _TEXT_SIDE.get(key)
-    if s is None:
-        s = _TEXT_SIDE[key] = torch.cuda.Stream(device)
-    return s
+    return streams.TEXT.get(device).stream if _forks(text_stream_enabled, device, single_gpu_only=False) else None
 
 
-def is_text_side_stream(stream):
-    return any(s.cuda_stream == stream.cuda_stream for s in _TEXT_SIDE.values())
-
-
-def join_text_streams():
-    """The current stream waits for every text side stream that was forked from it (gradient ranges about to go on the wire)."""
-    if not _TEXT_SIDE:
-        return
-    import torch
-    for (idx, handle), s in _TEXT_SIDE.items():
-        cur = torch.cuda.current_stream(idx)
-        if cur.cuda_stream == handle:
-            cur.wait_stream(s)
+is_text_side_stream = streams.TEXT.owns
+join_text_streams = streams.TEXT.join     # the current stream waits for every text side stream that was forked from it (gradient ranges about to go on the wire)
 
 
 # Third session: the frozen prompter's pass (get_pseudo_labels: a no-grad B-clip encoder forward, itself two half batches on two streams)
@@ -250,41 +240,19 @@ def join_text_streams():
 # instead of after them.  Forked at the START of the forward it ran beside the visual encoder's forward and cost +0.2 ... +0.7 % (profiles/r6_split_streams_ab.txt:
 # big beside big); forked behind it: 150.47 -> 150.09 ms (-0.25 %, A/B/A/B on one box, run-to-run spread 0.03 ms; profiles/r6_prompter_side_stream_ab.txt),
 # labels bit for bit.  ALPRO_PROMPTER_STREAM = 0 | 1 (default 1).
-_prompter_stream = [os.environ.get("ALPRO_PROMPTER_STREAM", "1") != "0"]
-_PROMPTER_SIDE = {}
-
-
-def set_prompter_stream(v):
-    _prompter_stream[0] = bool(v)
-
-
-def prompter_stream_enabled():
-    return _prompter_stream[0]
+prompter_stream_enabled = _Switch("prompter_stream", "ALPRO_PROMPTER_STREAM", "1")
+set_prompter_stream = prompter_stream_enabled.set
 
 
 def prompter_side_stream(device):
-    if not (_prompter_stream[0] and device.type == "cuda") or (_several_ranks() and os.environ.get("ALPRO_PROMPTER_STREAM") != "force"):
-        return None
-    import torch
-    key = (device.index if device.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(device).cuda_stream)
-    s = _PROMPTER_SIDE.get(key)
-    if s is None:
-        s = _PROMPTER_SIDE[key] = torch.cuda.Stream(device)
-    return s
+    return streams.PROMPTER.get(device).stream if _forks(prompter_stream_enabled, device) else None
 
 
 # Round 6: the no-grad Block.forward keeps the block input until both attention halves are done -- the add + norm1 kernel reads it and writes only the
 # normalised rows, the add + norm2 kernel adds the temporal AND the spatial branch (alpro_add_layernorm_pre_mlp2; bit for bit the same sums).
 # ALPRO_DEFER_TEMPORAL_ADD=0: the round-3 form (x + temporal branch written by the first kernel), for A/B.
-_defer_tadd = [os.environ.get("ALPRO_DEFER_TEMPORAL_ADD", "1") != "0"]
-
-
-def defer_temporal_add():
-    return _defer_tadd[0]
-
-
-def set_defer_temporal_add(v):
-    _defer_tadd[0] = bool(v)
+defer_temporal_add = _defer_tadd = _Switch("defer_temporal_add", "ALPRO_DEFER_TEMPORAL_ADD", "1")
+set_defer_temporal_add = defer_temporal_add.set
 
 
 # Recompute the ViT blocks' activations in backward.  Off (default): the anchored visual backward keeps every activation
@@ -292,64 +260,21 @@ def set_defer_temporal_add(v):
 # attention-dropout seeds (~3 KB per row) and its forward_train body runs once more right before its backward -- the same kernels on the same
 # operands, so outputs, gradients and both random streams are those of the stored step bit for bit, at the price of one more ViT training forward.
 # ALPRO_RECOMPUTE = 0 | 1 (default 0), read at every _VisualRun.forward.  `video_enc_cfg.gradient_checkpointing` does NOT set it.
-def _recompute_from_env():
-    v = os.environ.get("ALPRO_RECOMPUTE", "0").strip()
+def _zero_or_one(v):
+    v = v.strip()
     if v not in ("0", "1"):
         raise ValueError("ALPRO_RECOMPUTE=%r: expected 0 (keep every ViT block activation, the default) or 1 (recompute them in backward)" % v)
     return v == "1"
 
 
-_recompute = [_recompute_from_env()]
+recompute_blocks = _Switch("recompute", "ALPRO_RECOMPUTE", "0", parse=_zero_or_one)
+set_recompute = recompute_blocks.set
 
 
-def recompute_blocks():
-    return _recompute[0]
-
-
-def set_recompute(flag):
-    _recompute[0] = bool(flag)
-
-
-class use_recompute:
+def use_recompute(flag):
     """Context manager: `with use_recompute(True): loss = model(batch); loss.backward()` (the switch is read by the forward; the backward
     follows what its forward kept)."""
-
-    def __init__(self, flag):
-        self.flag = flag
-
-    def __enter__(self):
-        self.prev = recompute_blocks()
-        set_recompute(self.flag)
-
-    def __exit__(self, *a):
-        set_recompute(self.prev)
-
-
-def wgrad_side_event(device):
-    """An event behind every weight gradient launched so far on the side stream of the current launch stream, or None if there is none."""
-    if device.type != "cuda":
-        return None
-    key = (device.index if device.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(device).cuda_stream)
-    ent = _WGRAD_SIDE.get(key)
-    return ent[0].record_event() if (ent is not None and ent[1]) else None
-
-
-def set_cls_precise(v):
-    _cls_precise[0] = v.lower() if isinstance(v, str) else ("1" if v else "0")
-
-
-class use_cls_precise:
-    """`with use_cls_precise(False): ...` (tests, bench.py's mode table)."""
-
-    def __init__(self, v):
-        self.v = v
-
-    def __enter__(self):
-        self.prev = _cls_precise[0]
-        set_cls_precise(self.v)
-
-    def __exit__(self, *a):
-        _cls_precise[0] = self.prev
+    return override(recompute=flag)
 
 
 class cls_precise_off:
@@ -370,7 +295,6 @@ _armed = [None]     # weakref to the most recently attached LossScaler
 
 
 def set_armed_loss_scaler(scaler):
-    import weakref
     _armed[0] = weakref.ref(scaler) if scaler is not None else None
 
 
@@ -421,6 +345,11 @@ _drop_state = [None, 0]
 def seed_dropout(seed):
     _drop_state[0] = int(seed) & 0x7FFFFFFF
     _drop_state[1] = 0
+
+
+def dropout_state():
+    """(seed, counter) of the stream: the seed is None until first use, the counter is the number of seeds drawn since seed_dropout()."""
+    return tuple(_drop_state)
 
 
 def _auto_seed():

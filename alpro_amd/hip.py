@@ -8,6 +8,8 @@ import os
 
 import torch
 
+from alpro_amd import streams
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ALPRO_HIP_LIB") or os.path.join(_HERE, "lib", "libalpro_hip.so")  # ALPRO_HIP_LIB: another build of the library
 
@@ -83,11 +85,14 @@ def load():
     if _lib is not None:
         return _lib
     hq = os.environ.get("GPU_MAX_HW_QUEUES")
-    if hq and hq.isdigit() and int(hq) > 4 and any(os.environ.get(k, "1") != "0" for k in ("ALPRO_WGRAD_STREAM", "ALPRO_TEXT_STREAM", "ALPRO_PROMPTER_STREAM")):
-        import warnings
-        warnings.warn("alpro_amd: GPU_MAX_HW_QUEUES=%s -- with more than 4 hardware queues the training step's side streams (ALPRO_WGRAD_STREAM / "
-                      "ALPRO_TEXT_STREAM / ALPRO_PROMPTER_STREAM) measured 11 %% SLOWER than with the runtime's default of 4 (profiles/r6_hw_queues.txt): "
-                      "a fifth queue shares a dispatch pipe with the launch stream's" % hq)
+    if hq and hq.isdigit() and int(hq) > 4:
+        from alpro_amd import config as rt
+        step_streams = [rt.SWITCHES[n] for n in ("wgrad_stream", "text_stream", "prompter_stream")]
+        if any(os.environ.get(s.env, s.default) != "0" for s in step_streams):
+            import warnings
+            warnings.warn("alpro_amd: GPU_MAX_HW_QUEUES=%s -- with more than 4 hardware queues the training step's side streams (%s) measured 11 %% SLOWER "
+                          "than with the runtime's default of 4 (profiles/r6_hw_queues.txt): a fifth queue shares a dispatch pipe with the launch stream's"
+                          % (hq, " / ".join(s.env for s in step_streams)))
     if not os.path.exists(LIB_PATH):
         raise RuntimeError("libalpro_hip.so not found at %s -- run `python -m alpro_amd.build` "
                            "(there is no CPU fallback for the ALPRO hot path)" % LIB_PATH)
@@ -1089,7 +1094,7 @@ _TN_WORKSPACE = {}  # (device index, raw stream handle) -> grow-only byte buffer
 def _tn_workspace(device, nbytes):
     """The workspace of the CURRENT stream: its users run in stream order, so one buffer per (device, stream) is enough -- and a second
     stream (the weight-gradient side stream of alpro_amd.modeling.train.wgrad) must not share the launch stream's."""
-    key = (device.index, torch.cuda.current_stream(device).cuda_stream)
+    key = streams.key(device)
     ws = _TN_WORKSPACE.get(key)
     if ws is None or ws.numel() < nbytes:
         ws = _TN_WORKSPACE[key] = torch.empty(max(nbytes, 64 << 20), dtype=torch.uint8, device=device)

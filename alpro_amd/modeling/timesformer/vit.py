@@ -31,6 +31,7 @@ import torch.nn as nn
 
 from alpro_amd import config as rt
 from alpro_amd import hip
+from alpro_amd import streams
 from alpro_amd.modeling import train as tr
 from alpro_amd.modeling.weights import OperandCache, param_version
 
@@ -89,7 +90,7 @@ class Attention(nn.Module):
         self.attn_drop = nn.Dropout(attn_drop)
 
 
-class _ClsSide:
+class _ClsSide(streams.Side):
     """The precise-CLS chain of the ViT blocks on a second stream (alpro_amd.config.cls_stream, round 5).
 
     Per block the chain is: LayerNorm + q | k | v of the B CLS rows (needs only the block INPUT's CLS rows: the temporal half never touches
@@ -102,25 +103,8 @@ class _ClsSide:
         main (next block):  [wait done] before its first read of the CLS rows (the add + norm1 kernel)
     so the first part runs beside the temporal half and the second beside the MLP GEMMs.  All side-stream outputs live in buffers owned by
     this object (no allocation crosses streams); the event order above is also what makes their re-use from block to block safe."""
-    _by_device = {}
-
-    def __init__(self, device):
-        self.stream = torch.cuda.Stream(device)
-        self.bufs = {}
-        self.done = None
-
-    @classmethod
-    def _key(cls, device):
-        # one chain (side stream + buffers) per LAUNCH stream: the two-stream block runner (run_blocks) drives two of them at once
-        return (device.type, device.index if device.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(device).cuda_stream)
-
-    @classmethod
-    def get(cls, device):
-        key = cls._key(device)
-        obj = cls._by_device.get(key)
-        if obj is None:
-            obj = cls._by_device[key] = cls(device)
-        return obj
+    def __init__(self, stream):
+        self.stream, self.bufs, self.done = stream, {}, None
 
     def buf(self, name, shape, device):
         t = self.bufs.get((name, shape))
@@ -134,23 +118,19 @@ class _ClsSide:
             torch.cuda.current_stream().wait_event(self.done)
             self.done = None
 
-    @classmethod
-    def join(cls, device):
-        """The current stream waits for the chain that was driven from it."""
-        obj = cls._by_device.get(cls._key(device)) if device.type == "cuda" else None
-        if obj is not None:
-            obj.wait_done()
+
+# one chain (side stream + buffers) per LAUNCH stream: the two-stream block runner (run_blocks) drives two of them at once
+_CLS_SIDES = streams.SideStreams("cls", _ClsSide)
 
 
-_AUX_STREAMS = {}
+def join_cls_chain(device):
+    """The current stream waits for the precise-CLS chain that was driven from it."""
+    side = _CLS_SIDES.peek(device)
+    if side is not None:
+        side.wait_done()
 
 
-def _aux_stream(device):
-    key = (device.index if device.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(device).cuda_stream)
-    s = _AUX_STREAMS.get(key)
-    if s is None:
-        s = _AUX_STREAMS[key] = torch.cuda.Stream(device)
-    return s
+_ClsSide.join = staticmethod(join_cls_chain)
 
 
 def _draws_per_call(blk):
@@ -217,7 +197,7 @@ class _Collector:
     def block_end(self, tok):
         self.i += 1
         if self.want_hidden:
-            _ClsSide.join(tok.device)   # a precise-CLS chain on its side stream still writes the block output's CLS rows
+            join_cls_chain(tok.device)   # a precise-CLS chain on its side stream still writes the block output's CLS rows
             self.hidden.append(tok.detach().clone())
 
     def add_temporal(self, qkv, lse, T, H, scale):
@@ -242,7 +222,7 @@ def _run_collecting(blocks, tok, B, T, W, collect):
     for blk in blocks:
         tok = blk(tok, B, T, W, collect=collect.block_begin())
         collect.block_end(tok)
-    _ClsSide.join(tok.device)
+    join_cls_chain(tok.device)
     return tok
 
 
@@ -259,7 +239,7 @@ def run_prefix_blocks(blocks, tok, B, T, W, collect=None):
         if any(_draws_per_call(blk) for blk in blocks):
             for blk in blocks:
                 tok = blk(tok, B, T, W)
-            _ClsSide.join(tok.device)
+            join_cls_chain(tok.device)
             return tok
         return run_blocks(blocks, tok, B, T, W)
 
@@ -281,10 +261,10 @@ def run_blocks(blocks, tok, B, T, W, collect=None):
     if not (tok.is_cuda and not torch.is_grad_enabled() and rt.split_streams(B)):
         for blk in blocks:
             tok = blk(tok, B, T, W)
-        _ClsSide.join(dev)
+        join_cls_chain(dev)
         return tok
     from alpro_amd.modeling import weights
-    main, aux = torch.cuda.current_stream(dev), _aux_stream(dev)
+    main, aux = torch.cuda.current_stream(dev), streams.HALF.get(dev).stream
     h = B // 2
     lo, hi = tok[:h], tok[h:]
     lockstep = rt.split_lockstep()
@@ -310,10 +290,10 @@ def run_blocks(blocks, tok, B, T, W, collect=None):
                 ev = None
             blk(hi, h, T, W, **kw_hi)
             if lockstep or i == len(blocks) - 1:
-                _ClsSide.join(dev)
+                join_cls_chain(dev)
                 ev_hi = aux.record_event()
         if lockstep or i == len(blocks) - 1:
-            _ClsSide.join(dev)
+            join_cls_chain(dev)
             main.wait_event(ev_hi)
             if lockstep:
                 ev = main.record_event()
@@ -501,7 +481,7 @@ class Block(nn.Module):
             seeds = ap_t, seed_t, ap_s, seed_s = replay["attn_drop"] if replay is not None else self._attn_drop_seeds()   # the backward regenerates the masks from these
         # precise CLS rows, decided once: off (cp False) | on the launch stream (cp, side None) | on the side stream (side)
         cp = merged and not cls_only and (rt.cls_precise(dt) if cls_precise is None else cls_precise)
-        side = _ClsSide.get(dev) if (cp and rt.cls_stream(save) and x.is_cuda) else None
+        side = _CLS_SIDES.get(dev) if (cp and rt.cls_stream(save) and x.is_cuda) else None
         ev_mid = None
         if side is not None:
             x_cls_in, cls_q, o_c_buf = self._cls_side_begin(side, x, B, T, snapshot=not save)
@@ -632,7 +612,7 @@ class Block(nn.Module):
         The operand copies (16-bit weights, merged projection) are the step's: parameters must not have changed since the first pass."""
         B, T = slim["dims"][0], slim["dims"][1]
         out, sv = self._forward(slim["x"], B, T, save=True, drop_masks=(slim["drop_t"], slim["drop_s"], slim["drop_m"]), replay=slim, cls_precise=cls_precise)
-        _ClsSide.join(out.device)
+        join_cls_chain(out.device)
         return sv
 
     def _wt(self, name, lin, dt):
@@ -1251,12 +1231,12 @@ class _VisualRun:
             if collect is not None:   # (the maps are already taken, inside the block: before the saved dict is cut down below)
                 collect.block_end(tok)
             if self.recompute:
-                _ClsSide.join(tok.device)   # a precise-CLS chain on its side stream still writes x2's CLS rows: it is through before x2 is released
+                join_cls_chain(tok.device)   # a precise-CLS chain on its side stream still writes x2's CLS rows: it is through before x2 is released
                 sv, full = Block.slim_saved(sv), sv
                 full.clear()
                 del full
             self.saved.append(sv)
-        _ClsSide.join(tok.device)
+        join_cls_chain(tok.device)
         self.tok = tok
         if self.mode == hip.POOL_TEMPORAL:
             out32, _ = hip.vit_final_pool(tok, m.norm.weight, m.norm.bias, VIT_EPS, B, T, N, torch.float32)

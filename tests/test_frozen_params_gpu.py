@@ -282,13 +282,8 @@ def test_frozen_prefix_skips_its_blocks_and_matches_the_all_trainable_step(retri
             frozen = set(_freeze(m, names))
             with monkeypatch.context() as mp:
                 hits = _spy_blocks(vblocks + layers, mp)
-                prev = (rt._fuse_tattn[0], rt._split_streams[0], rt.defer_temporal_add())
-                if plain:
-                    rt.set_fuse_temporal_attention("0"); rt.set_split_streams("0"); rt.set_defer_temporal_add(False)
-                try:
+                with rt.override(**(dict(fuse_temporal_attention="0", split_streams="0", defer_temporal_add=False) if plain else {})):
                     out, g, vid = _step(m, batch, mode, loss_of, mp)
-                finally:
-                    rt.set_fuse_temporal_attention(prev[0]); rt.set_split_streams(prev[1]); rt.set_defer_temporal_add(prev[2])
             # frozen: no gradient; trainable: one
             assert [n for n in frozen if g[n] is not None] == [], tag
             missing = [n for n in g0 if n not in frozen and g0[n] is not None and g[n] is None]
@@ -397,7 +392,7 @@ def test_frozen_prefix_keeps_drop_path_attention_dropout_and_the_seed_stream(sma
         vit.sample_drop_paths(m.blocks, 2, T, N, tok.device)
         for blk in m.blocks[:K]:
             tok = blk(tok, 2, T, W)
-        vit._ClsSide.join(tok.device)
+        vit.join_cls_chain(tok.device)
         for blk in m.blocks:
             blk._presampled = None
         # ... and not its eval-mode forward
@@ -405,7 +400,7 @@ def test_frozen_prefix_keeps_drop_path_attention_dropout_and_the_seed_stream(sma
         tok_eval, _, _, _ = m._embed(x)
         for blk in m.blocks[:K]:
             tok_eval = blk(tok_eval, 2, T, W)
-        vit._ClsSide.join(tok.device)
+        vit.join_cls_chain(tok.device)
         enc.train()
     torch.cuda.synchronize()
     assert torch.equal(prefix_out, tok)
@@ -434,18 +429,16 @@ def test_frozen_prefix_on_two_streams_applies_the_masks_drawn_for_the_step(small
     for blk in enc.model.blocks[1:K]:
         blk.drop_path.drop_prob = 0.5                    # (the prefix blocks' own rates are 2-4 %: make a wrong mask show)
     _freeze(enc, ["model.patch_embed.", "model.cls_token", "model.pos_embed", "model.time_embed"] + ["model.blocks.%d." % i for i in range(K)])
-    prev_split = rt._split_streams[0]
     try:
         outs = {}
         for split in ("0", "1"):
-            rt.set_split_streams(split)
-            run, _ = _visual_run(enc, x, mode)
+            with rt.override(split_streams=split):
+                run, _ = _visual_run(enc, x, mode)
             assert run.nfro == K
             outs[split] = run.saved[0]["x"].clone()
             for s_ in run.saved:
                 s_.clear()
     finally:
-        rt.set_split_streams(prev_split)
         for d in drops:
             d.p = 0.1
         for blk, r in zip(enc.model.blocks[1:K], rates):

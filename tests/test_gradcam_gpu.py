@@ -116,7 +116,7 @@ def test_a_collector_changes_no_output_gradient_or_dropout_draw(model, mode, var
                     o = m(encoder_embeds=xs[0], attn_grads=col, **kw)
                 scaled_backward((o.last_hidden_state * w).sum(), dtype)
             torch.cuda.synchronize()
-            res.append((o.last_hidden_state.detach().clone(), [x.grad.clone() for x in xs], [p.grad.clone() for p in params], list(rt._drop_state), col))
+            res.append((o.last_hidden_state.detach().clone(), [x.grad.clone() for x in xs], [p.grad.clone() for p in params], list(rt.dropout_state()), col))
     finally:
         m.eval()
         _clear(m)
@@ -329,9 +329,9 @@ def test_text_to_patch_gradcam_is_the_mean_of_the_windowed_cams_and_leaves_the_m
         maps = {}
         for dtype in ("fp32", "fp16"):
             with rt.use_compute_dtype(dtype):
-                seeds = list(rt._drop_state)
+                seeds = list(rt.dropout_state())
                 got = text_to_patch_gradcam(pair, ids, mask, video, layers=layers)
-                assert list(rt._drop_state) == seeds
+                assert list(rt.dropout_state()) == seeds
                 assert [p.requires_grad for p in pair.parameters()] == flags
                 assert all(a is b for a, b in zip(grads, [p.grad for p in pair.parameters()]))
                 assert torch.equal(m.encoder.layer[3].output.dense.bias.grad, marker)

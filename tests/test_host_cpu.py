@@ -1334,8 +1334,7 @@ def test_round6_forward_schedule_switches(monkeypatch):
     block runner stays on the plain path whenever the split cannot apply."""
     from alpro_amd import config as rt
     from alpro_amd.modeling.timesformer import vit
-    prev = (rt._split_streams[0], rt._defer_tadd[0])
-    try:
+    with rt.override("split_streams", "defer_temporal_add"):
         rt.set_split_streams("auto")
         assert [rt.split_streams(b) for b in (1, 2, 8, 15, 16, 17, 32, 64)] == [False, False, False, False, True, False, True, True]
         rt.set_split_streams("1")
@@ -1360,9 +1359,6 @@ def test_round6_forward_schedule_switches(monkeypatch):
         with torch.no_grad():
             out = vit.run_blocks([Blk(), Blk()], tok, 4, 2, 14)
         assert out is tok and calls == [(4, 4), (4, 4)]
-    finally:
-        rt.set_split_streams(prev[0])
-        rt.set_defer_temporal_add(prev[1])
     # weight gradients on a side stream: only inside an anchored backward, only on a GPU tensor's device, only when switched on
     prev_w = rt.wgrad_stream_enabled()
     try:
@@ -1370,8 +1366,7 @@ def test_round6_forward_schedule_switches(monkeypatch):
         assert rt.wgrad_side_stream(torch.device("cpu")) is None
         rt.wgrad_scope(True)
         assert rt.wgrad_side_stream(torch.device("cpu")) is None      # CPU tensors never fork a stream
-        rt.wgrad_scope(False)
-        assert rt._wgrad_active[0] == 0
+        assert rt.wgrad_scope(False) == 0
         rt.join_wgrad()                                                # nothing pending: a no-op without a GPU
         # a job with several ranks keeps the weight-gradient and prompter side streams off (launch + collective + text + the prompter's second half = the
         # four hardware queues): asked for a CUDA device, both decline BEFORE touching the runtime

@@ -706,8 +706,7 @@ def test_cls_chain_on_a_side_stream_is_result_neutral():
     x = torch.randn(B, 3, T, 224, 224, device="cuda")
     dout = torch.randn(B, 197, 768, device="cuda") * 1e-2
     res = {}
-    prev = rt._cls_stream[0]
-    try:
+    with rt.override("cls_stream"):
         for on in (False, True, True, False):
             rt.set_cls_stream(on)
             with rt.use_compute_dtype("bf16"), rt.use_cls_precise("1"):
@@ -729,8 +728,6 @@ def test_cls_chain_on_a_side_stream_is_result_neutral():
             else:
                 for a, b, what in zip(cur, res["ref"], ("forward_features", "forward_cls", "training forward", "parameter gradients")):
                     assert torch.equal(a, b), "%s differs with cls_stream=%s" % (what, on)
-    finally:
-        rt.set_cls_stream(prev)
     assert bool(torch.isfinite(res["ref"][3]).all()) and float(res["ref"][3].abs().sum()) > 0
 
 
@@ -751,12 +748,10 @@ def test_fused_temporal_half_against_the_two_launches(mode):
             torch.nn.init.normal_(blk.temporal_fc.weight, std=0.02)
     x = torch.randn(B, 3, T, 224, 224, device="cuda")
     dout = torch.randn(B, 197, 768, device="cuda") * 1e-2
-    prev = rt._fuse_tattn[0]
     res = {}
     try:
         for fuse in ("0", "1"):
-            rt.set_fuse_temporal_attention(fuse)
-            with rt.use_compute_dtype(mode), rt.use_cls_precise("0"):
+            with rt.override(fuse_temporal_attention=fuse), rt.use_compute_dtype(mode), rt.use_cls_precise("0"):
                 enc.eval()
                 with torch.no_grad():
                     y = enc.forward_features(x).float().clone()
@@ -773,7 +768,6 @@ def test_fused_temporal_half_against_the_two_launches(mode):
             torch.cuda.synchronize()
             res[fuse] = (y, c, yt.detach().float().clone(), g)
     finally:
-        rt.set_fuse_temporal_attention(prev)
         rt.set_armed_loss_scaler(None)
     eps = {"fp16": 2.0 ** -10, "bf16": 2.0 ** -7}[mode]
     for i, what in enumerate(("forward_features", "forward_cls", "training forward")):
@@ -839,12 +833,9 @@ def test_side_stream_backward_is_handed_to_the_callers_stream():
     still holds -- this torch's engine orders the caller's stream behind every stream a backward node ran on by itself (a plain autograd.Function on
     a side stream shows the same) -- so the callback is the documented guarantee for engines that do not, and this test pins the property either way.
     The streams are picked among eight candidates that demonstrably run beside the launch stream."""
-    from alpro_amd import config as rt
+    from alpro_amd import config as rt, streams
     from alpro_amd.modeling import train as tr
     dev = torch.device("cuda", torch.cuda.current_device())
-    prev_t, prev_w = rt.text_stream_enabled(), rt.wgrad_stream_enabled()
-    rt.set_text_stream(True)
-    rt.set_wgrad_stream(True)
     seen = {}
 
     class Run:
@@ -881,56 +872,47 @@ def test_side_stream_backward_is_handed_to_the_callers_stream():
         torch.cuda.synchronize()
         return float(early.item()) == 0.0
     main = torch.cuda.current_stream(dev)
-    key = (dev.index, main.cuda_stream)
-    prev_side, prev_wside = rt._TEXT_SIDE.get(key), rt._WGRAD_SIDE.copy()
-    try:
+    with rt.override(text_stream=True, wgrad_stream=True):
         cands = [torch.cuda.Stream(dev) for _ in range(8)]
         free = [c for c in cands if runs_beside(main, c)]
         assert len(free) >= 2, "no stream of eight runs beside the launch stream on this box"
-        rt._TEXT_SIDE[key] = free[0]                 # the text side stream of this launch stream ...
-        rt._WGRAD_SIDE[key] = [free[1], False]       # ... and its weight-gradient side stream
-        side = rt.text_side_stream(dev)
-        assert side is free[0] and side.cuda_stream != main.cuda_stream
-        # no gradient flows OUT of the runs to a tensor of the caller's stream (as with the text encoder: token ids in, parameters only) -- otherwise the
-        # engine's own producer -> consumer ordering for that gradient would hide a missing hand-over
-        x = torch.ones(8, device=dev)
-        p = torch.nn.Parameter(torch.zeros(1, device=dev))
-        # (a)
-        a = Run("a")
-        a.buf = torch.zeros(4, device=dev)
-        torch.cuda.synchronize()
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            y = tr.run_anchored(a, [x], [p])
-        main.wait_stream(side)
-        y.record_stream(main)
-        assert y.requires_grad
-        y.sum().backward()
-        got_a = a.buf.clone()     # queued on the caller's stream right behind backward(): no device-wide sync in between
-        torch.cuda.synchronize()
-        assert seen["a_stream"] == side.cuda_stream, "autograd did not run the anchored backward on the stream of its forward"
-        assert seen["a_wgrad_side"] is None, "a backward on the text side stream was given a side stream of its own"
-        assert got_a.tolist() == [7.0] * 4, "the caller's stream read the side stream's write too early: %s" % got_a.tolist()
-        # (b)
-        b = Run("b")
-        b.buf = torch.zeros(4, device=dev)
-        torch.cuda.synchronize()
-        y = tr.run_anchored(b, [x], [p])
-        y.sum().backward()
-        got_b = b.buf.clone()
-        torch.cuda.synchronize()
-        assert seen["b_stream"] == main.cuda_stream and seen["b_wgrad_side"] is free[1], "no weight-gradient side stream inside an anchored backward on the launch stream"
-        assert got_b.tolist() == [9.0] * 4, "the weight-gradient side stream was not joined where the backward returned: %s" % got_b.tolist()
-    finally:
-        torch.cuda.synchronize()
-        rt.set_text_stream(prev_t)
-        rt.set_wgrad_stream(prev_w)
-        if prev_side is None:
-            rt._TEXT_SIDE.pop(key, None)
-        else:
-            rt._TEXT_SIDE[key] = prev_side
-        rt._WGRAD_SIDE.clear()
-        rt._WGRAD_SIDE.update(prev_wside)
+        # the text side stream of this launch stream ... and its weight-gradient side stream
+        with streams.TEXT.installed(free[0], dev), streams.WGRAD.installed(free[1], dev):
+            try:
+                side = rt.text_side_stream(dev)
+                assert side is free[0] and side.cuda_stream != main.cuda_stream
+                # no gradient flows OUT of the runs to a tensor of the caller's stream (as with the text encoder: token ids in, parameters only) -- otherwise the
+                # engine's own producer -> consumer ordering for that gradient would hide a missing hand-over
+                x = torch.ones(8, device=dev)
+                p = torch.nn.Parameter(torch.zeros(1, device=dev))
+                # (a)
+                a = Run("a")
+                a.buf = torch.zeros(4, device=dev)
+                torch.cuda.synchronize()
+                side.wait_stream(main)
+                with torch.cuda.stream(side):
+                    y = tr.run_anchored(a, [x], [p])
+                main.wait_stream(side)
+                y.record_stream(main)
+                assert y.requires_grad
+                y.sum().backward()
+                got_a = a.buf.clone()     # queued on the caller's stream right behind backward(): no device-wide sync in between
+                torch.cuda.synchronize()
+                assert seen["a_stream"] == side.cuda_stream, "autograd did not run the anchored backward on the stream of its forward"
+                assert seen["a_wgrad_side"] is None, "a backward on the text side stream was given a side stream of its own"
+                assert got_a.tolist() == [7.0] * 4, "the caller's stream read the side stream's write too early: %s" % got_a.tolist()
+                # (b)
+                b = Run("b")
+                b.buf = torch.zeros(4, device=dev)
+                torch.cuda.synchronize()
+                y = tr.run_anchored(b, [x], [p])
+                y.sum().backward()
+                got_b = b.buf.clone()
+                torch.cuda.synchronize()
+                assert seen["b_stream"] == main.cuda_stream and seen["b_wgrad_side"] is free[1], "no weight-gradient side stream inside an anchored backward on the launch stream"
+                assert got_b.tolist() == [9.0] * 4, "the weight-gradient side stream was not joined where the backward returned: %s" % got_b.tolist()
+            finally:
+                torch.cuda.synchronize()
 
 
 def test_pretrain_step_never_makes_the_host_wait_for_the_device(fixture_models):
@@ -969,7 +951,7 @@ def test_text_pass_on_its_side_stream_is_bitwise_neutral(fixture_models, monkeyp
     encoder's forward, its backward (autograd: on the stream of the forward) beside the visual encoder's backward; the launch stream waits where the
     text rows are first needed and takes the side stream's parameter gradients over in an end-of-backward callback.  Every output of the pretraining
     forward and every parameter gradient must be bit for bit what the one-stream step gives -- twice each, alternating, on the 8-frame fixture model."""
-    from alpro_amd import config as rt
+    from alpro_amd import config as rt, streams
     m, batch, _ = fixture_models("pretrain_T8")
     monkeypatch.setattr(torch, "multinomial", argmax_multinomial)
     monkeypatch.setattr(np.random, "uniform", lambda *a, **k: 1.0)      # use_mask_prob branch not taken, on every pass
@@ -989,7 +971,7 @@ def test_text_pass_on_its_side_stream_is_bitwise_neutral(fixture_models, monkeyp
             cur.append(torch.cat([p.grad.reshape(-1).float() for p in m.parameters() if p.grad is not None]).clone())
             torch.cuda.synchronize()
             if side:
-                assert rt._TEXT_SIDE, "the side stream was never created"
+                assert streams.TEXT.entries, "the side stream was never created"
             if ref is None:
                 ref = cur
                 assert bool(torch.isfinite(ref[-1]).all()) and float(ref[-1].abs().sum()) > 0
@@ -1008,7 +990,7 @@ def test_weight_gradients_on_the_side_stream_are_bitwise_neutral(mode):
     are launched on a second HIP stream behind an event of the launch stream, which waits for them where the backward returns.  Same kernels, same
     operands, same summation order: every parameter gradient of the encoder's training forward + hand-written backward must be bit for bit what
     the one-stream backward leaves (three backward passes each, the later ones into warm allocator blocks that the side stream has used)."""
-    from alpro_amd import config as rt
+    from alpro_amd import config as rt, streams
     from alpro_amd.modeling.timesformer.vit import TimeSformer
     torch.manual_seed(41)
     T, B = 4, 8
@@ -1038,8 +1020,8 @@ def test_weight_gradients_on_the_side_stream_are_bitwise_neutral(mode):
                         res["ref"] = g
                     assert torch.equal(g, res["ref"]), "parameter gradients differ (side stream %s, pass %d): max %.3e" % (side, rep, float((g - res["ref"]).abs().max()))
             if side:
-                ent = [e for e in rt._WGRAD_SIDE.values()]
-                assert ent and all(not e[1] for e in ent), "the side stream was not used, or not joined where the backward returned"
+                ent = [e for e in streams.WGRAD.entries.values()]
+                assert ent and all(not e.pending for e in ent), "the side stream was not used, or not joined where the backward returned"
     finally:
         rt.set_wgrad_stream(prev)
         rt.set_armed_loss_scaler(None)
@@ -1067,30 +1049,24 @@ def test_inference_forward_schedules_are_bitwise_neutral(mode):
             torch.nn.init.normal_(blk.temporal_fc.weight, std=0.02)
             torch.nn.init.normal_(blk.temporal_fc.bias, std=0.02)
     x = torch.randn(B, 3, T, 224, 224, device="cuda")
-    prev = (rt._defer_tadd[0], rt._split_streams[0], rt._cls_stream[0], os.environ.get("ALPRO_SPLIT_LOCKSTEP"))
+    prev = os.environ.get("ALPRO_SPLIT_LOCKSTEP")
     outs = {}
     try:
         for cp in ("0", "1"):
             for defer in (False, True):
                 for split, lock, cs in (("0", "0", "0"), ("1", "0", "0"), ("1", "0", "infer"), ("1", "1", "infer")):
-                    rt.set_defer_temporal_add(defer)
-                    rt.set_split_streams(split)
-                    rt.set_cls_stream(cs)
                     os.environ["ALPRO_SPLIT_LOCKSTEP"] = lock
-                    with rt.use_compute_dtype(mode), rt.use_cls_precise(cp), torch.no_grad():
+                    with rt.override(defer_temporal_add=defer, split_streams=split, cls_stream=cs), rt.use_compute_dtype(mode), rt.use_cls_precise(cp), torch.no_grad():
                         for rep in range(2):   # twice: the second pass runs with warm operand copies (no fork-after-rebuild event)
                             y = enc.forward_features(x).float().clone()
                             c = enc.forward_cls(x).float().clone()
                     torch.cuda.synchronize()
                     outs[(cp, defer, split, lock, cs)] = (y, c)
     finally:
-        rt.set_defer_temporal_add(prev[0])
-        rt.set_split_streams(prev[1])
-        rt.set_cls_stream(prev[2])
-        if prev[3] is None:
+        if prev is None:
             os.environ.pop("ALPRO_SPLIT_LOCKSTEP", None)
         else:
-            os.environ["ALPRO_SPLIT_LOCKSTEP"] = prev[3]
+            os.environ["ALPRO_SPLIT_LOCKSTEP"] = prev
     for cp in ("0", "1"):
         ref = outs[(cp, False, "0", "0", "0")]
         assert bool(torch.isfinite(ref[0]).all()) and float(ref[0].abs().sum()) > 0

@@ -59,7 +59,7 @@ def run(enc, x, pooling, mode, x_grad=True, probe=None, seed=None, recompute=Fal
     torch.cuda.synchronize()
     grads = {n: p.grad.clone() for n, p in enc.named_parameters() if p.grad is not None}
     mp.fresh_grads(enc)
-    return out.detach(), (None if xr.grad is None else xr.grad / gs), grads, list(rt._drop_state)
+    return out.detach(), (None if xr.grad is None else xr.grad / gs), grads, list(rt.dropout_state())
 
 
 @pytest.mark.parametrize("pooling", POOLINGS)
@@ -231,11 +231,11 @@ def test_full_chain_pixel_gradient_and_saliency(chain, mode):
         flags = [q.requires_grad for q in m.parameters()]
         grads = [q.grad for q in m.parameters()]
         with rt.use_compute_dtype(mode):
-            seeds = list(rt._drop_state)
+            seeds = list(rt.dropout_state())
             g = pixel_gradient(m, ids, mask, clips)
             sal_g = text_to_pixel_saliency(m, ids, mask, clips, method="grad")
             sal_x = text_to_pixel_saliency(m, ids, mask, clips)
-            assert list(rt._drop_state) == seeds
+            assert list(rt.dropout_state()) == seeds
             assert [q.requires_grad for q in m.parameters()] == flags
             assert all(a is b for a, b in zip(grads, [q.grad for q in m.parameters()]))
             assert torch.equal(m.visual_encoder.model.norm.bias.grad, marker)

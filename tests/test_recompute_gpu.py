@@ -33,13 +33,13 @@ def test_block_replay_rebuilds_the_saved_dict_bit_for_bit_and_draws_nothing(B, T
     rt.seed_dropout(4242)
     with rt.use_compute_dtype(mode), torch.no_grad():
         out, sv = blk.forward_train(x.clone(), B, T, W)
-        vit._ClsSide.join(out.device)
+        vit.join_cls_chain(out.device)
         torch.cuda.synchronize()
         assert sv["attn_drop"][1] and sv["attn_drop"][3]
         ref = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in sv.items()}
         slim = vit.Block.slim_saved(sv)
         sv.clear()
-    drop_state, cpu_rng, gpu_rng = list(rt._drop_state), torch.get_rng_state(), torch.cuda.get_rng_state()
+    drop_state, cpu_rng, gpu_rng = list(rt.dropout_state()), torch.get_rng_state(), torch.cuda.get_rng_state()
     blk._drop = None                  # the replay may not ask for a mask ...
     blk._presampled = {B: None}       # ... nor look at the pre-sampled ones
     blk.eval()                        # ... nor read the module's mode
@@ -47,7 +47,7 @@ def test_block_replay_rebuilds_the_saved_dict_bit_for_bit_and_draws_nothing(B, T
         got = blk.replay(slim, W, cls_precise=rt.cls_precise(ref["dt"]))
     torch.cuda.synchronize()
     assert blk._presampled == {B: None}
-    assert list(rt._drop_state) == drop_state
+    assert list(rt.dropout_state()) == drop_state
     assert torch.equal(torch.get_rng_state(), cpu_rng) and torch.equal(torch.cuda.get_rng_state(), gpu_rng)
     assert set(got) == set(ref)
     rows_t = B * N * T
@@ -93,7 +93,7 @@ def _enc_step(e, x, dout, mode, recompute, pooling="temporal"):
     torch.cuda.synchronize()
     rt.set_armed_loss_scaler(None)
     grads = {n: (None if p.grad is None else p.grad.clone()) for n, p in e.named_parameters()}
-    return dict(out=out.detach().clone(), grads=grads, drop=list(rt._drop_state), cpu=torch.get_rng_state(), gpu=torch.cuda.get_rng_state())
+    return dict(out=out.detach().clone(), grads=grads, drop=list(rt.dropout_state()), cpu=torch.get_rng_state(), gpu=torch.cuda.get_rng_state())
 
 
 def _same_step(a, b, what):
@@ -132,8 +132,7 @@ def test_encoder_step_fp16_variants(enc, variant):
     from alpro_amd import config as rt
     pooling = "spatial" if variant == "pooling_spatial" else "temporal"
     x, dout = _enc_inputs(pooling)
-    prev = (rt.wgrad_stream_enabled(), rt._fuse_tattn[0], rt._cls_stream[0])
-    try:
+    with rt.override("wgrad_stream", "fuse_temporal_attention", "cls_stream"):
         if variant == "wgrad_stream_off":
             rt.set_wgrad_stream(False)
         elif variant == "fused_temporal_training_form":
@@ -142,8 +141,6 @@ def test_encoder_step_fp16_variants(enc, variant):
             rt.set_cls_stream("1")                         # the precise-CLS chain of the training forward -- and of the replay -- on its side stream
         off = _enc_step(enc, x, dout, "fp16", False, pooling)
         on = _enc_step(enc, x, dout, "fp16", True, pooling)
-    finally:
-        rt.set_wgrad_stream(prev[0]); rt.set_fuse_temporal_attention(prev[1]); rt.set_cls_stream(prev[2])
     _same_step(on, off, variant)
 
 

@@ -151,13 +151,13 @@ def test_block_attn_dropout_eval_and_p0_draw_nothing(mode):
     rt.seed_dropout(7)
     with rt.use_compute_dtype(mode), torch.no_grad():
         assert torch.equal(blk(x.clone(), B, T, W), blk0(x.clone(), B, T, W))
-    assert rt._drop_state[1] == 0
+    assert rt.dropout_state()[1] == 0
     blk0.train()
     _, _, _, seeds0 = _run(blk0, x, dout, B, T, W, mode)
-    assert seeds0 == (0.0, 0, 0.0, 0) and rt._drop_state[1] == 0
+    assert seeds0 == (0.0, 0, 0.0, 0) and rt.dropout_state()[1] == 0
     with rt.use_compute_dtype(mode), torch.no_grad():
         blk0(x.clone(), B, T, W)
-    assert rt._drop_state[1] == 0
+    assert rt.dropout_state()[1] == 0
 
 
 @pytest.mark.gpu
@@ -169,7 +169,7 @@ def test_block_attn_dropout_train_mode_properties(mode):
     out0, _, _, _ = _run(blk0, x, dout, B, T, W, mode)
     # p > 0: two seeds per block and step, another output, and the same bits when the seed counter is reset
     out1, dx1, g1, seeds1 = _run(blk, x, dout, B, T, W, mode)
-    assert rt._drop_state[1] == 2, rt._drop_state
+    assert rt.dropout_state()[1] == 2, rt.dropout_state()
     assert not torch.equal(out1, out0)
     out2, dx2, g2, seeds2 = _run(blk, x, dout, B, T, W, mode)
     assert seeds2 == seeds1
@@ -183,7 +183,7 @@ def test_block_attn_dropout_train_mode_properties(mode):
     rt.seed_dropout(4242)
     with rt.use_compute_dtype(mode), torch.no_grad():
         y = blk(x.clone(), B, T, W)
-    assert rt._drop_state[1] == 2, rt._drop_state
+    assert rt.dropout_state()[1] == 2, rt.dropout_state()
     err, lim = float((y - out1).abs().max()), 2 * TOL[mode] * float(out1.abs().max())
     print("[attn-dropout no_grad vs autograd path %s] err %.3e limit %.3e; p=0 vs p=0.1 differ by %.3e" % (mode, err, lim, float((out1 - out0).abs().max())))
     assert err <= lim, (err, lim)
@@ -200,8 +200,7 @@ def test_block_attn_dropout_skips_the_fused_temporal_launch():
     blk, _, x, dout = _pair(B, T, W)
     h = torch.empty((B * N * T, D), dtype=torch.float16, device="cuda")
     assert hip.qkv_tattn_ok(h, T)
-    old = rt._fuse_tattn[0]
-    try:
+    with rt.override("fuse_temporal_attention"):
         res = {}
         for fuse in ("0", "1"):
             rt.set_fuse_temporal_attention(fuse)
@@ -209,7 +208,5 @@ def test_block_attn_dropout_skips_the_fused_temporal_launch():
             rt.seed_dropout(4242)
             with rt.use_compute_dtype("fp16"), torch.no_grad():
                 res[fuse] += (blk(x.clone(), B, T, W),)
-    finally:
-        rt._fuse_tattn[0] = old
     assert torch.equal(res["1"][0], res["0"][0]) and torch.equal(res["1"][1], res["0"][1]) and torch.equal(res["1"][4], res["0"][4])
     assert all(torch.equal(res["1"][2][n], res["0"][2][n]) for n in res["0"][2])

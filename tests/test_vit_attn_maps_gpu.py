@@ -117,7 +117,7 @@ def test_features_are_bitwise_what_they_are_without_the_flags_eval(cases, full, 
 def _streams():
     """What the next draws of the three random streams are: the dropout-seed counter, the device generator, the CPU generator."""
     from alpro_amd import config as rt
-    return tuple(rt._drop_state), torch.rand(4, device="cuda").cpu(), torch.rand(4)
+    return rt.dropout_state(), torch.rand(4, device="cuda").cpu(), torch.rand(4)
 
 
 def _seed():
@@ -218,15 +218,11 @@ def test_sixteen_clips_collect_on_one_stream(cases, mode):
     geo = dict(img=32, T=2, B=16)
     x = pool_clips(geo).cuda()
     B, T, N = 16, 2, 4
-    prev = rt._split_streams[0]
     with rt.use_compute_dtype(mode), torch.no_grad():
         assert rt.split_streams(B)
         out = enc.forward_features(x, output_attentions=True, output_hidden_states=True)
-        rt.set_split_streams(False)
-        try:
+        with rt.override(split_streams=False):
             one = enc.forward_features(x)
-        finally:
-            rt._split_streams[0] = prev
     assert torch.equal(out.features, one)
     assert tuple(out.temporal_attentions[0].shape) == (B * N, H, T, T) and tuple(out.spatial_attentions[-1].shape) == (B * T, H, 1 + N, 1 + N)
     for m in out.spatial_attentions + out.temporal_attentions:
@@ -298,15 +294,10 @@ def test_cls_rows_of_the_hidden_states(cases, full, mode, name):
     with torch.no_grad():
         direct, _ = hip.vit_final_pool(out.hidden_states[-1].clone(), m.norm.weight, m.norm.bias, vit.VIT_EPS, B, T, N, torch.float32)
     assert torch.equal(direct, out.features)
-    prev = rt._cls_stream[0]
     runs = {}
-    try:
-        for v in ("1", "0"):
-            rt.set_cls_stream(v)
-            with rt.use_compute_dtype(mode), torch.no_grad():
-                runs[v] = enc.forward_features(x, output_hidden_states=True)
-    finally:
-        rt._cls_stream[0] = prev
+    for v in ("1", "0"):
+        with rt.override(cls_stream=v), rt.use_compute_dtype(mode), torch.no_grad():
+            runs[v] = enc.forward_features(x, output_hidden_states=True)
     assert torch.equal(runs["1"].features, runs["0"].features)
     for i in range(DEPTH + 1):
         assert torch.equal(runs["1"].hidden_states[i][:, 0], runs["0"].hidden_states[i][:, 0]), "CLS rows of hidden state %d" % i

@@ -18,7 +18,7 @@ CLS_TOL = {"fp32": 2e-5, "fp16": 4e-3}   # tests/test_model_parity.py::test_forw
 @pytest.mark.parametrize("B,T,W", [(2, 2, 4), (2, 3, 3)])   # 64 temporal rows (the fused temporal launch takes them), L = 17 | T = 3: the windowed temporal kernel, L = 10
 def test_block_entry_points_agree(B, T, W, mode, merge):
     from alpro_amd import config as rt
-    from alpro_amd.modeling.timesformer.vit import _ClsSide
+    from alpro_amd.modeling.timesformer.vit import join_cls_chain
     N = W * W
     blk = _block(0.0).eval()
     blk.merge_temporal_proj = merge
@@ -35,7 +35,7 @@ def test_block_entry_points_agree(B, T, W, mode, merge):
         # (i) forward and forward_train, under the fixed drop-path scales of the attention-dropout tests (one clip's MLP branch dropped)
         _fix_drop_path(blk, B, T, N)
         y = blk(x.clone(), B, T, W)
-        _ClsSide.join(x.device)   # the precise-CLS chain of the in-place forward runs on its side stream by default
+        join_cls_chain(x.device)  # the precise-CLS chain of the in-place forward runs on its side stream by default
         out = blk.forward_train(x.clone(), B, T, W)[0]
         err, lim = float((y - out).abs().max()), 2 * TOL[mode] * float(out.abs().max())
         print("[block paths %s merge=%d T=%d] forward vs forward_train: err %.3e limit %.3e" % (mode, merge, T, err, lim))

@@ -99,7 +99,7 @@ def config(name, run, training):
     rt.seed_dropout(4242)
     torch.cuda.reset_peak_memory_stats()
     res = run()
-    vit._ClsSide.join(torch.device("cuda"))
+    vit.join_cls_chain(torch.device("cuda"))
     torch.cuda.synchronize()
     for k in sorted(res):
         OUT.write("sha %s %s\n" % (k, hashlib.sha256(res[k].detach().contiguous().view(torch.uint8).cpu().numpy().tobytes()).hexdigest()))
