@@ -88,12 +88,6 @@ __global__ __launch_bounds__(MAP_THREADS) void tprobs_tile_kernel(const T* __res
   }
 }
 
-inline int64_t tp_items(int64_t rows, int T, int H) {
-  if (32 % T == 0) return ((rows + 31) / 32) * H;
-  const int64_t nt = (T + 31) / 32;
-  return (rows / T) * H * nt * nt;
-}
-
 template <typename T>
 int launch_tprobs(const void* qkv, const float* lse, float* out, int64_t rows, int Tn, int H, float scale, hipStream_t st) {
   const int64_t items = tp_items(rows, Tn, H);
@@ -115,12 +109,7 @@ using namespace alpro;
 
 extern "C" int alpro_attn_temporal_probs(const void* qkv, const float* lse, float* out, int dtype, int64_t rows, int T, int H, float scale, void* stream) {
   // every check in front of the first HIP call: the refusals are testable without a device
-  ALPRO_CHECK(dtype == ALPRO_F32 || dtype == ALPRO_BF16 || dtype == ALPRO_F16, "alpro_attn_temporal_probs: dtype=%d (ALPRO_F32, ALPRO_BF16 or ALPRO_F16)", dtype);
-  ALPRO_CHECK(T >= 1 && T <= ALPRO_ATTN_MAX_T, "alpro_attn_temporal_probs: num_frm=%d unsupported (1..%d = ALPRO_ATTN_MAX_T)", T, ALPRO_ATTN_MAX_T);
-  ALPRO_CHECK(rows >= 0 && rows % T == 0, "alpro_attn_temporal_probs: rows=%lld not a non-negative multiple of T=%d", (long long)rows, T);
-  ALPRO_CHECK(H >= 1, "alpro_attn_temporal_probs: H=%d (need >= 1)", H);
-  ALPRO_CHECK((tp_items(rows, T, H) + MAP_WAVES - 1) / MAP_WAVES <= INT_MAX, "alpro_attn_temporal_probs: rows=%lld x H=%d at T=%d needs more than 2^31 - 1 workgroups",
-              (long long)rows, H, T);
+  if (int rc = map_temporal_check("alpro_attn_temporal_probs", dtype, rows, T, H)) return rc;
   if (rows == 0) return ALPRO_OK;
   ALPRO_CHECK(qkv != nullptr, "alpro_attn_temporal_probs: null qkv");
   ALPRO_CHECK(lse != nullptr, "alpro_attn_temporal_probs: null lse");

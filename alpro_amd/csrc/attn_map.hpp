@@ -1,5 +1,5 @@
 // What the kernels that MATERIALISE attention maps share (attention_probs.hip: text / fusion maps; attention_probs_grad.hip: their gradient and Grad-CAM;
-// attention_temporal_probs.hip: the visual encoder's temporal maps).  The forward / backward kernels are flash-style and never hold P; they leave
+// attention_temporal_probs.hip: the visual encoder's temporal maps; attention_temporal_probs_grad.hip: their gradient and Grad-CAM).  The forward / backward kernels are flash-style and never hold P; they leave
 // lse, the natural-log normaliser over all keys of a row, so a map is p = exp(s - lse) of a score s recomputed here -- pre-dropout probabilities.
 //
 // Layout: no LDS, no K / V residency.  Every operand is a 64-wide head row straight from global memory as MFMA operand chunks: lane l holds row
@@ -77,6 +77,25 @@ inline int map_window_check(const char* fn, bool grad, int dtype, int batch, int
   ALPRO_CHECK(((uintptr_t)qkv % 16) == 0 && ((uintptr_t)dctx % 16) == 0 && ((uintptr_t)out % 16) == 0 && ((uintptr_t)cam_out % 16) == 0,
               "%s: %s must be 16-byte aligned", fn, grad ? "qkv, dctx, grad_out and cam_out" : "qkv and out");
   ALPRO_CHECK(((uintptr_t)lse % 4) == 0 && ((uintptr_t)key_bias % 4) == 0, "%s: lse and key_bias must be 4-byte aligned", fn);
+  return ALPRO_OK;
+}
+
+// Work items of the temporal map kernels (attention_temporal_probs.hip, attention_temporal_probs_grad.hip), one wave each: T dividing 32 -> a
+// (32-row unit, head); any other T -> a (group, head, 32-query tile, 32-key tile)
+inline int64_t tp_items(int64_t rows, int T, int H) {
+  if (32 % T == 0) return ((rows + 31) / 32) * H;
+  const int64_t nt = (T + 31) / 32;
+  return (rows / T) * H * nt * nt;
+}
+
+// The shape checks of the temporal entry points (fn: the one that was called), in front of their rows == 0 return.  Host only, no HIP call.
+inline int map_temporal_check(const char* fn, int dtype, int64_t rows, int T, int H) {
+  ALPRO_CHECK(dtype == ALPRO_F32 || dtype == ALPRO_BF16 || dtype == ALPRO_F16, "%s: dtype=%d (ALPRO_F32, ALPRO_BF16 or ALPRO_F16)", fn, dtype);
+  ALPRO_CHECK(T >= 1 && T <= ALPRO_ATTN_MAX_T, "%s: num_frm=%d unsupported (1..%d = ALPRO_ATTN_MAX_T)", fn, T, ALPRO_ATTN_MAX_T);
+  ALPRO_CHECK(rows >= 0 && rows % T == 0, "%s: rows=%lld not a non-negative multiple of T=%d", fn, (long long)rows, T);
+  ALPRO_CHECK(H >= 1, "%s: H=%d (need >= 1)", fn, H);
+  ALPRO_CHECK((tp_items(rows, T, H) + MAP_WAVES - 1) / MAP_WAVES <= INT_MAX, "%s: rows=%lld x H=%d at T=%d needs more than 2^31 - 1 workgroups", fn,
+              (long long)rows, H, T);
   return ALPRO_OK;
 }
 

@@ -8,6 +8,9 @@ The fusion maps are collapsed over time (the fusion encoder sees temporally pool
 which frame, is in the maps of its divided space-time blocks: frame_patch_attention returns the frame's [CLS] query row of the spatial maps
 (again a window: no (1+N, 1+N) map is formed), patch_temporal_attention the (T, T) temporal map of every patch position.
 
+Which patches of which frame, and which frames, made a caption match: frame_patch_gradcam and patch_temporal_gradcam are Grad-CAM
+(P * relu(d ITM score / d P)) on those two sets of maps -- the one quantity of ViT explanation that is local in time.
+
 At pixel resolution, per frame: pixel_gradient is d ITM score / d visual_inputs through the fusion layers, the visual encoder and the patch
 embedding; text_to_pixel_saliency reduces its channels (input gradient, gradient x input).
 """
@@ -259,3 +262,72 @@ def patch_temporal_attention(encoder, visual_inputs, layers=(-1,)):
         m = out.temporal_attentions[pick.index(int(l) % depth)].mean(dim=1)
         acc = m if acc is None else acc + m
     return (acc / float(len(layers))).view(B, hg, wg, T, T)
+
+
+def _vit_gradcam(model, text_input_ids, text_input_mask, visual_inputs, layers, target, grad_scale, what, spatial):
+    """The shared body of frame_patch_gradcam (spatial) and patch_temporal_gradcam: -> (B, T, Hg, Wg, list of the chosen blocks' CAM head means)."""
+    from alpro_amd import config as rt
+    from alpro_amd.modeling.alpro_models import _linear32
+    from alpro_amd.modeling.timesformer.vit import VitAttnGradients
+    if model.training:
+        raise RuntimeError("%s inspects a trained model: call model.eval() first (no dropout, no drop-path, no RNG draw)" % what)
+    B, T, hg, wg = _grid(visual_inputs, what)
+    if text_input_ids.dim() != 2 or text_input_ids.shape != text_input_mask.shape or text_input_ids.shape[0] != B:
+        raise ValueError("%s: text_input_ids %s / text_input_mask %s are not (B=%d, Lt), one caption per clip of visual_inputs %s"
+                         % (what, tuple(text_input_ids.shape), tuple(text_input_mask.shape), B, tuple(visual_inputs.shape)))
+    grad_scale = _power_of_two_scale(grad_scale, what)
+    depth = len(model.visual_encoder.model.blocks)
+    pick = _block_mean(range(depth), layers, what)
+    collector = VitAttnGradients(layers=pick, want=("cam",), spatial=spatial, temporal=not spatial,
+                                 spatial_window=((0, 1), (1, 1 + hg * wg)) if spatial else None, grad_scale=grad_scale)
+    flags = [(p, p.requires_grad) for p in model.parameters()]
+    try:
+        for p, _ in flags:
+            p.requires_grad_(False)
+        with torch.no_grad():
+            text_embeds = model._text_embeds(text_input_ids, text_input_mask)
+        clip = visual_inputs.detach().float()   # (needs no gradient: the backward stops at the first chosen block)
+        with torch.enable_grad():
+            video = model.visual_encoder.forward_features(clip.transpose(1, 2), return_all_tokens=True, attn_grads=collector)
+            video_atts = torch.ones((B, video.shape[1]), dtype=text_input_mask.dtype, device=text_input_mask.device)
+            out = model._fusion(torch.cat([text_embeds, video.to(text_embeds.dtype)], dim=1), torch.cat([text_input_mask, video_atts], dim=1))
+            score = _linear32(out[:, 0, :], model.itm_head)[:, int(target)].sum() * grad_scale
+            with rt.loss_scaling(collector):   # (marks the backward as scaled: config.check_backward_precision)
+                score.backward()
+    finally:
+        for p, f in flags:
+            p.requires_grad_(f)
+    cams = collector.spatial_cams if spatial else collector.temporal_cams
+    acc = None
+    for i in pick:   # head mean, then the layer mean
+        m = cams[i].mean(dim=1)
+        acc = m if acc is None else acc + m
+    res = acc / float(len(pick))
+    if not bool(torch.isfinite(res).all()):
+        raise RuntimeError("%s: the map is not finite at grad_scale=%g -- the scaled backward left fp16's range; pass a smaller power of two as grad_scale"
+                           % (what, grad_scale))
+    return B, T, hg, wg, res
+
+
+def frame_patch_gradcam(model, text_input_ids, text_input_mask, visual_inputs, layers=(-1,), target=1, grad_scale=None):
+    """Grad-CAM of the ITM score over the patches of every frame: arguments as pixel_gradient, plus `layers` (blocks of the visual encoder,
+    negative from the end; default: the last one).  Returns (B, T, Hg, Wg) fp32: P * relu(d score / d P) of the frame's [CLS] query against
+    the patches of ITS frame in the spatial attention -- the window ((0, 1), (1, 1 + N)), no (1+N, 1+N) tensor is formed --, averaged over the
+    heads, then over the chosen blocks, with score = itm_head(fusion [CLS])[:, target].sum() (target 1: "match") and P the softmax before
+    dropout.  Where frame_patch_attention says where a frame's [CLS] reads, this says which patches of which frame made the caption match;
+    text_to_patch_gradcam's map is the same question averaged over the frames.  With precise [CLS] rows P and G of this query row are the
+    16-bit graph's.
+    The text pass runs without grad; the visual and the fusion pass run with grad, but the clip needs no gradient: the backward goes through the
+    fusion layers and the visual blocks down to the first chosen one and stops there.  The model is left untouched, exactly as by
+    text_to_patch_gradcam (requires_grad False for the duration and restored, no .grad written, train.BACKWARD_EPOCH bumped); grad_scale as there:
+    a positive power of two, None = the initial scale of alpro_amd.amp.LossScaler under fp16, 1 otherwise; a non-finite map raises, no retry."""
+    B, T, hg, wg, res = _vit_gradcam(model, text_input_ids, text_input_mask, visual_inputs, layers, target, grad_scale, "frame_patch_gradcam", True)
+    return res.view(B, T, hg, wg)
+
+
+def patch_temporal_gradcam(model, text_input_ids, text_input_mask, visual_inputs, layers=(-1,), target=1, grad_scale=None):
+    """As frame_patch_gradcam, for the temporal half: returns (B, Hg, Wg, T, T) fp32, P * relu(d score / d P) of the temporal attention map
+    (query frame, key frame) of every patch position, averaged over the heads, then over the chosen blocks: which frames made the caption match,
+    and through which other frames."""
+    B, T, hg, wg, res = _vit_gradcam(model, text_input_ids, text_input_mask, visual_inputs, layers, target, grad_scale, "patch_temporal_gradcam", False)
+    return res.view(B, hg, wg, T, T)

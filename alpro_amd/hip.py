@@ -34,7 +34,7 @@ EXPORTS = ["alpro_hip_last_error", "alpro_hip_abi_version", "alpro_hip_set_optio
            "alpro_hip_sched_workspace_bytes", "alpro_hip_set_sched_workspace", "alpro_hip_release_stream", "alpro_gemm_qkv_tattn", "alpro_add_layernorm_pre_mlp2", "alpro_adamw_step_lp",
            "alpro_gemm_rows_f32_relu_mask", "alpro_clip_pool", "alpro_adamw_step_groups", "alpro_attn_temporal_fwd_drop", "alpro_attn_temporal_bwd_drop",
            "alpro_vit_final_pool_mode", "alpro_vit_final_pool_mode_bwd", "alpro_augment_stage", "alpro_augment_stats", "alpro_resized_crop",
-           "alpro_sim_topk", "alpro_sim_topk_workspace_bytes", "alpro_attn_probs", "alpro_attn_temporal_probs", "alpro_attn_probs_grad", "alpro_unpatchify"]
+           "alpro_sim_topk", "alpro_sim_topk_workspace_bytes", "alpro_attn_probs", "alpro_attn_temporal_probs", "alpro_attn_probs_grad", "alpro_unpatchify", "alpro_attn_temporal_probs_grad"]
 
 
 class GemmDesc(ctypes.Structure):
@@ -170,6 +170,7 @@ def load():
     lib.alpro_attn_probs.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, i32, i32, i32, vp]
     lib.alpro_attn_temporal_probs.argtypes = [vp, vp, vp, i32, i64, i32, i32, f32, vp]
     lib.alpro_attn_probs_grad.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, i32, i32, i32, i32, vp]
+    lib.alpro_attn_temporal_probs_grad.argtypes = [vp, vp, vp, vp, vp, i32, i64, i32, i32, f32, f32, vp]
     lib.alpro_unpatchify.argtypes = [vp, i32, vp, i32, i32, i32, i32, vp]
     if lib.alpro_hip_abi_version() != ABI_VERSION:
         raise RuntimeError("libalpro_hip.so ABI version mismatch")
@@ -720,6 +721,18 @@ def attn_probs_grad(qkv, dctx, lse, batch, L, H, scale, key_bias=None, q_range=N
     return res if len(res) > 1 else res[0]
 
 
+def _temporal_probs_args(fn, qkv, lse, H):
+    """The qkv / lse shape checks attn_temporal_probs and attn_temporal_probs_grad share (fn: the caller, for the messages) -> rows."""
+    if qkv.dtype not in _CODE or qkv.dim() != 2 or qkv.shape[1] != 3 * H * 64 or not qkv.is_contiguous():
+        raise RuntimeError("%s: qkv must be a contiguous (rows, 3*H*64) = (rows, %d) fp32 / bf16 / fp16 tensor (got %s %s, strides %s)"
+                           % (fn, 3 * H * 64, qkv.dtype, tuple(qkv.shape), tuple(qkv.stride())))
+    rows = qkv.shape[0]
+    if lse.dtype != torch.float32 or tuple(lse.shape) != ((rows + 31) // 32, H, 32) or not lse.is_contiguous():
+        raise RuntimeError("%s: lse must be a contiguous ((rows + 31) // 32, H, 32) = (%d, %d, 32) fp32 tensor (got %s %s)"
+                           % (fn, (rows + 31) // 32, H, lse.dtype, tuple(lse.shape)))
+    return rows
+
+
 def attn_temporal_probs(qkv, lse, T, H, scale):
     """The softmax probabilities attn_temporal() / gemm_qkv_tattn() never materialise (alpro_attn_temporal_probs): qkv (rows, 3*H*64) as the temporal
     qkv Linear wrote it, lse ((rows + 31) // 32, H, 32) fp32 from attn_temporal(..., want_lse=True) or gemm_qkv_tattn(..., want_qkv=True) on the same
@@ -727,17 +740,35 @@ def attn_temporal_probs(qkv, lse, T, H, scale):
     _need_dev("attn_temporal_probs", ("qkv", qkv), ("lse", lse))
     lib = load()
     T, H = int(T), int(H)
-    if qkv.dtype not in _CODE or qkv.dim() != 2 or qkv.shape[1] != 3 * H * 64 or not qkv.is_contiguous():
-        raise RuntimeError("attn_temporal_probs: qkv must be a contiguous (rows, 3*H*64) = (rows, %d) fp32 / bf16 / fp16 tensor (got %s %s, strides %s)"
-                           % (3 * H * 64, qkv.dtype, tuple(qkv.shape), tuple(qkv.stride())))
-    rows = qkv.shape[0]
-    if lse.dtype != torch.float32 or tuple(lse.shape) != ((rows + 31) // 32, H, 32) or not lse.is_contiguous():
-        raise RuntimeError("attn_temporal_probs: lse must be a contiguous ((rows + 31) // 32, H, 32) = (%d, %d, 32) fp32 tensor (got %s %s)"
-                           % ((rows + 31) // 32, H, lse.dtype, tuple(lse.shape)))
+    rows = _temporal_probs_args("attn_temporal_probs", qkv, lse, H)
     # (the library refuses T outside 1..128 and rows % T != 0; max(.., 1): such a call never divides by zero here)
     out = torch.empty((rows // max(T, 1), H, max(T, 0), max(T, 0)), dtype=torch.float32, device=qkv.device)
     _check(lib.alpro_attn_temporal_probs(_ptr(qkv), _ptr(lse), _ptr(out), _CODE[qkv.dtype], rows, T, H, float(scale), _stream()), "alpro_attn_temporal_probs")
     return out
+
+
+def attn_temporal_probs_grad(qkv, dctx, lse, T, H, scale, want=("grad", "cam"), grad_scale=1.0):
+    """The gradient w.r.t. the temporal softmax probabilities that attn_temporal_bwd() never materialises, and the Grad-CAM map
+    (alpro_attn_temporal_probs_grad): qkv / lse / T as for attn_temporal_probs; dctx (rows, H*64) in qkv's dtype, the gradient w.r.t.
+    attn_temporal()'s output as attn_temporal_bwd() takes it.  want: "grad" -> G = grad_scale * dctx . v, "cam" -> P * max(G, 0) with P bitwise
+    attn_temporal_probs' value; returns the requested (rows // T, H, T, T) fp32 tensors in the order of `want` (a single tensor for a single
+    name).  The gradient of the pre-dropout softmax: no dropout arguments."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or len(set(want)) != len(want) or any(w not in ("grad", "cam") for w in want):
+        raise RuntimeError("attn_temporal_probs_grad: want=%r (one or both of 'grad', 'cam', each once)" % (want,))
+    _need_dev("attn_temporal_probs_grad", ("qkv", qkv), ("dctx", dctx), ("lse", lse))
+    lib = load()
+    T, H = int(T), int(H)
+    rows = _temporal_probs_args("attn_temporal_probs_grad", qkv, lse, H)
+    if dctx.dtype != qkv.dtype or tuple(dctx.shape) != (rows, H * 64) or not dctx.is_contiguous():
+        raise RuntimeError("attn_temporal_probs_grad: dctx must be a contiguous (rows, H*64) = (%d, %d) %s tensor, the dtype of qkv (got %s %s, strides %s)"
+                           % (rows, H * 64, qkv.dtype, dctx.dtype, tuple(dctx.shape), tuple(dctx.stride())))
+    # (max(.., 1), max(.., 0): as in attn_temporal_probs)
+    outs = {w: torch.empty((rows // max(T, 1), H, max(T, 0), max(T, 0)), dtype=torch.float32, device=qkv.device) for w in want}
+    _check(lib.alpro_attn_temporal_probs_grad(_ptr(qkv), _ptr(dctx), _ptr(lse), _ptr(outs.get("grad")), _ptr(outs.get("cam")), _CODE[qkv.dtype], rows, T, H,
+                                              float(scale), float(grad_scale), _stream()), "alpro_attn_temporal_probs_grad")
+    res = tuple(outs[w] for w in want)
+    return res if len(res) > 1 else res[0]
 
 
 def qkv_tattn_ok(a, T):

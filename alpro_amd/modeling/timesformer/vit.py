@@ -22,6 +22,8 @@ arguments, `forward_features` signatures and the state_dict layout (`model.block
   forward hooks on attn.attn_drop / temporal_attn      forward_features(output_attentions=, output_hidden_states=): the maps are
   .attn_drop (the softmax of :92-93) and on the blocks  recomputed from q | k | v and the log-sum-exp rows (alpro_attn_probs,
                                                        alpro_attn_temporal_probs), the hidden states are copies -> VisualEncoderOutput
+  retain_grad() on the input of attn.attn_drop /       forward_features(attn_grads=VitAttnGradients(...)): the blocks' backward hands the collector
+  temporal_attn.attn_drop (:92-93)                     d(ctx) where it is final (alpro_attn_probs_grad, alpro_attn_temporal_probs_grad)
 """
 import math
 from functools import partial
@@ -209,6 +211,93 @@ class _Collector:
     def result(self, features):
         return VisualEncoderOutput(features, tuple(self.hidden) if self.want_hidden else None, tuple(self.spatial) if self.want_attn else None,
                                    tuple(self.temporal) if self.want_attn else None)
+
+
+class VitAttnGradients:
+    """Collects, during backward(), the gradient of whatever is differentiated w.r.t. the attention probabilities of the divided space-time blocks
+    of one pass (TimeSformer.forward_features attn_grads): G = d(score) / d(P) and the Grad-CAM map P * relu(G), fp32, keyed by block index i:
+      spatial_grads[i] / spatial_cams[i]     (B*T, H, nq, nk), batch index b*T + t: the (1+N, 1+N) map of every frame, or its spatial_window
+      temporal_grads[i] / temporal_cams[i]   (B*N, H, T, T), batch index b*N + n: the map of every patch position
+    -- the layouts of VisualEncoderOutput's maps.  P is the softmax BEFORE dropout, bitwise the `spatial_attentions` / `temporal_attentions`
+    entry; G is what the reference leaves in .grad after retain_grad() on the input of attn.attn_drop / temporal_attn.attn_drop (vit.py:92-93).
+    One launch per chosen block and half (hip.attn_probs_grad, hip.attn_temporal_probs_grad), on the launch stream, right where the
+    hand-written backward holds the final d(ctx); the flash-style backward kernels never form either tensor.
+    layers: block indices, negative from the end (None: all); want: "grad", "cam" or both; spatial / temporal: which halves are collected;
+    spatial_window: ((q_start, q_stop), (k_start, k_stop)) over the 1 + N tokens of a frame, bit for bit the slice of the full map (the temporal
+    maps are always whole); grad_scale: the factor the differentiated score carries (a loss scale under fp16 operands): the kernels multiply G
+    by 1 / grad_scale.  With precise [CLS] rows the CLS query row's P and G are the 16-bit graph's (the one the backward differentiates), not
+    the fp32 re-evaluation's.  Drop-path in train mode is allowed (G is then that sampled graph's gradient); active attention dropout is not.
+    Reading a result before the backward has run through the chosen blocks raises."""
+
+    def __init__(self, layers=None, want=("cam",), spatial=True, temporal=True, spatial_window=None, grad_scale=1.0):
+        self.layers = None if layers is None else tuple(int(l) for l in layers)
+        self.want = (want,) if isinstance(want, str) else tuple(want)
+        if not self.want or len(set(self.want)) != len(self.want) or any(w not in ("grad", "cam") for w in self.want):
+            raise ValueError("VitAttnGradients: want=%r (one or both of 'grad', 'cam')" % (want,))
+        if self.layers is not None and not self.layers:
+            raise ValueError("VitAttnGradients: no layer chosen")
+        self.spatial, self.temporal = bool(spatial), bool(temporal)
+        if not (self.spatial or self.temporal):
+            raise ValueError("VitAttnGradients: spatial=False and temporal=False (nothing to collect)")
+        self.q_range = self.k_range = None
+        if spatial_window is not None:
+            try:
+                (q0, q1), (k0, k1) = spatial_window
+            except (TypeError, ValueError):
+                raise ValueError("VitAttnGradients: spatial_window must be ((q_start, q_stop), (k_start, k_stop)) over the 1 + N tokens of a frame (got %r)"
+                                 % (spatial_window,))
+            self.q_range, self.k_range = (int(q0), int(q1)), (int(k0), int(k1))
+        self.grad_scale = float(grad_scale)
+        if not self.grad_scale > 0 or not math.isfinite(self.grad_scale):
+            raise ValueError("VitAttnGradients: grad_scale=%r (a positive finite number)" % (grad_scale,))
+        self._pick, self._pending = (), None
+        self._store = {}
+
+    def begin(self, depth):
+        """A pass over `depth` blocks starts: resolve `layers` against it and forget what an earlier pass left."""
+        idx = range(depth) if self.layers is None else self.layers
+        for i in idx:
+            if not -depth <= i < depth:
+                raise ValueError("VitAttnGradients: block index %d outside -%d .. %d" % (i, depth, depth - 1))
+        self._pick = tuple(sorted(set(i % depth for i in idx)))
+        self._pending = set((half, i) for i in self._pick for half, on in (("spatial", self.spatial), ("temporal", self.temporal)) if on)
+        self._store = {(half, w): {} for half in ("spatial", "temporal") for w in ("grad", "cam")}
+
+    def wants(self, i):
+        return i in self._pick
+
+    def first(self):
+        return self._pick[0]
+
+    def _keep(self, half, i, res):
+        for w, t in zip(self.want, res if isinstance(res, tuple) else (res,)):
+            self._store[(half, w)][i] = t
+        self._pending.discard((half, i))
+
+    def add_spatial(self, i, qkv, dctx, lse, batch, L, H, scale):
+        if ("spatial", i) in self._pending:
+            self._keep("spatial", i, hip.attn_probs_grad(qkv, dctx, lse, batch, L, H, scale, q_range=self.q_range, k_range=self.k_range, want=self.want,
+                                                         grad_scale=1.0 / self.grad_scale))
+
+    def add_temporal(self, i, qkv, dctx, lse, T, H, scale):
+        if ("temporal", i) in self._pending:
+            self._keep("temporal", i, hip.attn_temporal_probs_grad(qkv, dctx, lse, T, H, scale, want=self.want, grad_scale=1.0 / self.grad_scale))
+
+    def _read(self, half, w):
+        what = "%s_%ss" % (half, w)
+        if self._pending is None:
+            raise RuntimeError("VitAttnGradients.%s: the collector was not passed to a TimeSformer.forward_features(attn_grads=...) yet" % what)
+        if self._pending:
+            raise RuntimeError("VitAttnGradients.%s: backward() has not run through %s yet"
+                               % (what, ", ".join("block %d (%s)" % (i, h) for h, i in sorted(self._pending, key=lambda e: (e[1], e[0])))))
+        if w not in self.want or not getattr(self, half):
+            raise RuntimeError("VitAttnGradients.%s: the collector was built with want=%r, spatial=%r, temporal=%r" % (what, self.want, self.spatial, self.temporal))
+        return self._store[(half, w)]
+
+    spatial_grads = property(lambda self: self._read("spatial", "grad"))
+    spatial_cams = property(lambda self: self._read("spatial", "cam"))
+    temporal_grads = property(lambda self: self._read("temporal", "grad"))
+    temporal_cams = property(lambda self: self._read("temporal", "cam"))
 
 
 def _collector(depth, output_attentions, output_hidden_states, attn_layers, attn_window):
@@ -439,10 +528,11 @@ class Block(nn.Module):
         rows of the masks drawn for the whole step).  collect: the _Collector that takes this block's attention maps, or None."""
         return self._forward(x, B, T, drop_masks=drop_masks, collect=collect)
 
-    def forward_train(self, x, B, T, W, collect=None):
+    def forward_train(self, x, B, T, W, collect=None, attn_grads=None):
         """Same arithmetic as forward() but out of place: fresh buffers (the backward needs every LayerNorm input); returns (out, saved) for the
-        explicit backward()."""
-        return self._forward(x, B, T, save=True, collect=collect)
+        explicit backward().  attn_grads: (VitAttnGradients, this block's index) -- kept in `saved` (and by slim_saved / replay), backward()
+        hands the collector d(ctx) of both attention halves."""
+        return self._forward(x, B, T, save=True, collect=collect, attn_grads=attn_grads)
 
     def forward_cls(self, x, B, T, W):
         """LAST block when only the CLS output is consumed (the frozen prompter: get_pseudo_labels uses feat = proj(x[:, 0])):
@@ -451,7 +541,7 @@ class Block(nn.Module):
         (vit.py:165-212); eval mode only (no drop-path).  Returns the block output's CLS rows, (B, D) fp32."""
         return self._forward(x, B, T, cls_only=True)
 
-    def _forward(self, x, B, T, save=False, cls_only=False, drop_masks=None, replay=None, cls_precise=None, collect=None):
+    def _forward(self, x, B, T, save=False, cls_only=False, drop_masks=None, replay=None, cls_precise=None, collect=None, attn_grads=None):
         """The divided space-time block (vit.py:146-212), every stage stated once.  The residual stream goes
             x --temporal branch--> xt --spatial branch--> x2 --MLP--> out
         and the three entry points differ in where those four live and in what is kept:
@@ -592,7 +682,8 @@ class Block(nn.Module):
             self._cls_chain(x_cls_in, o_c, B, T, drop_s, drop_m, x2_c, out[:, 0], side, ev_mid, ev_out)
         if not save:
             return out
-        return out, dict(x=x, dims=(B, T, N, S, D, H), dt=dt, drop_t=drop_t, drop_s=drop_s, drop_m=drop_m, attn_drop=seeds, merged=merged, u_tiled=u_tiled,
+        ag = {} if attn_grads is None else dict(attn_grads=attn_grads)   # (no key without a collector: the saved dict is the one it always was)
+        return out, dict(ag, x=x, dims=(B, T, N, S, D, H), dt=dt, drop_t=drop_t, drop_s=drop_s, drop_m=drop_m, attn_drop=seeds, merged=merged, u_tiled=u_tiled,
                          h=h, qkv_t=qkv_t, a_t=a_t, lse_t=lse_t, pr=pr, xt=xt, hs=hs, qkv_s=qkv_s, a_s=a_s, lse_s=lse_s, x2=x2, h2=h2, u=u, f1=f1)
 
     SLIM_KEYS = ("x", "drop_t", "drop_s", "drop_m", "attn_drop", "dims", "dt", "merged", "u_tiled")
@@ -602,7 +693,10 @@ class Block(nn.Module):
         """What recomputation keeps of forward_train's saved dict (alpro_amd.config.recompute_blocks): the block input, the three drop-path scale
         vectors, the attention-dropout tuple and the scalars -- a dict of its own, so clearing `sv` releases every other activation and leaves this
         one whole.  Pure: no device work."""
-        return {k: sv[k] for k in Block.SLIM_KEYS}
+        slim = {k: sv[k] for k in Block.SLIM_KEYS}
+        if "attn_grads" in sv:   # (collector, block index): the replayed dict hands them to backward() again
+            slim["attn_grads"] = sv["attn_grads"]
+        return slim
 
     def replay(self, slim, W, cls_precise=None):
         """slim_saved(...) of an earlier forward_train -> the full saved dict again, by running the same _forward body on the kept input with the
@@ -611,7 +705,8 @@ class Block(nn.Module):
         joined here, before anyone reads the rebuilt x2 and before the block output, which nobody needs, is released.
         The operand copies (16-bit weights, merged projection) are the step's: parameters must not have changed since the first pass."""
         B, T = slim["dims"][0], slim["dims"][1]
-        out, sv = self._forward(slim["x"], B, T, save=True, drop_masks=(slim["drop_t"], slim["drop_s"], slim["drop_m"]), replay=slim, cls_precise=cls_precise)
+        out, sv = self._forward(slim["x"], B, T, save=True, drop_masks=(slim["drop_t"], slim["drop_s"], slim["drop_m"]), replay=slim, cls_precise=cls_precise,
+                                attn_grads=slim.get("attn_grads"))
         join_cls_chain(out.device)
         return sv
 
@@ -698,6 +793,9 @@ class Block(nn.Module):
         tr.wgrad(dpo, sv["a_s"], sa.proj.weight, sa.proj.bias)
         da = tr.dgrad(dpo, self._wt("s_proj", sa.proj, dt))
         del dpo
+        ag, ag_i = sv.get("attn_grads") or (None, None)
+        if ag is not None:   # d(ctx) of the spatial half is final: G = da v^T and P * relu(G), which the flash-style backward below never forms
+            ag.add_spatial(ag_i, sv["qkv_s"], da, sv["lse_s"], B * T, N + 1, H, sa.scale)
         dqkv = hip.attn_bwd(sv["qkv_s"], sv["a_s"], da, sv["lse_s"], B * T, N + 1, H, sa.scale, drop_p=ap_s, drop_seed=seed_s)
         tr.wgrad(dqkv, sv["hs"], sa.qkv.weight, sa.qkv.bias)
         dhs = tr.dgrad(dqkv, self._wt("s_qkv", sa.qkv, dt))
@@ -719,6 +817,8 @@ class Block(nn.Module):
             dpp = tr.dgrad(dfo, self._wt("t_fc", self.temporal_fc, dt), row_scale=sv["drop_t"], row_scale_group=T)
             tr.wgrad(dpp, sv["a_t"], ta.proj.weight, ta.proj.bias)
             da = tr.dgrad(dpp, self._wt("t_proj", ta.proj, dt))
+        if ag is not None:   # ... and of the temporal half, on the merged and on the unmerged projection path
+            ag.add_temporal(ag_i, sv["qkv_t"], da, sv["lse_t"], T, H, ta.scale)
         dqkv = hip.attn_temporal_bwd(sv["qkv_t"], sv["a_t"], da, sv["lse_t"], T, H, ta.scale, drop_p=ap_t, drop_seed=seed_t)
         tr.wgrad(dqkv, sv["h"], ta.qkv.weight, ta.qkv.bias)
         dh = tr.dgrad(dqkv, self._wt("t_qkv", ta.qkv, dt))
@@ -1108,7 +1208,7 @@ class TimeSformer(nn.Module):
     POOLING = {'temporal': hip.POOL_TEMPORAL, 'spatial': hip.POOL_SPATIAL, 'none': hip.POOL_NONE}   # vit.py:489
 
     def forward_features(self, x, return_all_tokens=True, pooling='temporal', output_attentions=False, output_hidden_states=False, attn_layers=None,
-                         attn_window=None):
+                         attn_window=None, attn_grads=None):
         """x: (b, c, t, h, w); the final LayerNorm fused with the pooling (vit.py:475-503), n = h*w/256 patches per frame:
           'temporal' -> (b, 1 + n, 768)     CLS, then every patch averaged over the frames
           'spatial'  -> (b, 1 + t, 768)     CLS, then every frame averaged over its patches
@@ -1128,7 +1228,26 @@ class TimeSformer(nn.Module):
         attn_layers: block indices (negative: from the end) whose maps are collected; None = all 12.  Mind the size: the full set at B = 8 clips of
         8 frames at 224 px is 12 x (64, 12, 197, 197) fp32 = 1.4 GB of spatial maps.
         attn_window: ((q_start, q_stop), (k_start, k_stop)) over the 1 + N tokens of a frame: only this window of every spatial map is formed, bit
-        for bit the slice of the full map (the temporal maps are always whole)."""
+        for bit the slice of the full map (the temporal maps are always whole).
+
+        attn_grads (this repo's extension; the reference: retain_grad() on the input of attn.attn_drop / temporal_attn.attn_drop): a
+        VitAttnGradients.  The backward of whatever is computed from the result fills it with d(score) / d(P) and / or P * relu(d score / d P) of
+        the chosen blocks' spatial and temporal maps (see that class).  The pass is anchored even when no parameter is trainable and the clip
+        needs no gradient: the frozen prefix then ends in front of the first chosen block and the frozen blocks behind it run their data-only
+        backward (no .grad is written).  It changes no bit of `features`, of a gradient or of a random stream, and combines with the flags above.
+        Refused: grad mode off (no backward would run), and a chosen block whose attention dropout is active (the maps are the pre-dropout
+        softmax's; call model.eval()).  Drop-path in train mode is allowed."""
+        if attn_grads is not None:   # host-side refusals, in front of any device work
+            if not isinstance(attn_grads, VitAttnGradients):
+                raise TypeError("forward_features(attn_grads=...): a VitAttnGradients collector is needed (got %s)" % type(attn_grads).__name__)
+            if not torch.is_grad_enabled():
+                raise RuntimeError("forward_features(attn_grads=...): grad mode is off (torch.no_grad / inference_mode) -- no backward will run, the collector would stay empty")
+            attn_grads.begin(len(self.model.blocks))
+            for i in attn_grads._pick:
+                blk = self.model.blocks[i]
+                if blk.training and (blk.attn.attn_drop.p > 0 or blk.temporal_attn.attn_drop.p > 0):
+                    raise RuntimeError("forward_features(attn_grads=...): block %d has active attention dropout (train mode, attn_drop_rate > 0) -- the collected "
+                                       "maps are the pre-dropout softmax's and its gradient; call model.eval() first" % i)
         assert return_all_tokens, "forward_features(return_all_tokens=False) is not supported (the reference fails on it: vit.py:484 indexes the 2-D CLS tensor with three subscripts)"
         assert pooling in ['temporal', 'spatial', 'none'], 'Invalid pooling type {}'.format(pooling)
         mode = self.POOLING[pooling]
@@ -1140,6 +1259,12 @@ class TimeSformer(nn.Module):
                                                                                                                self.num_frames, self.img_size, self.num_frames, G, G))
         m = self.model
         collect = _collector(len(m.blocks), output_attentions, output_hidden_states, attn_layers, attn_window)
+        if attn_grads is not None:
+            # anchored whatever requires a gradient: a fresh scalar rides along as the one "parameter" that makes autograd schedule the node when
+            # nothing else does (its gradient is None)
+            rider = torch.zeros((), dtype=torch.float32, device=x.device, requires_grad=True)
+            out = tr.run_anchored(_VisualRun(self, mode, collect, attn_grads), [x], list(self.parameters()) + [rider])
+            return out if collect is None else collect.result(out)
         if torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters()) or x.requires_grad):   # (x.requires_grad: the pixel gradient)
             out = tr.run_anchored(_VisualRun(self, mode, collect), [x], list(self.parameters()))
             return out if collect is None else collect.result(out)
@@ -1193,9 +1318,10 @@ class TimeSformer(nn.Module):
 class _VisualRun:
     """Forward/backward of the whole visual encoder for tr.Anchor (alpro_models.py:186-194 under autograd)."""
 
-    def __init__(self, enc, mode=hip.POOL_TEMPORAL, collect=None):
+    def __init__(self, enc, mode=hip.POOL_TEMPORAL, collect=None, attn_grads=None):
         self.enc, self.mode = enc, mode   # mode: the pooling behind the final norm (hip.POOL_*)
         self.collect = collect            # a _Collector (output_attentions / output_hidden_states) or None
+        self.attn_grads = attn_grads      # a VitAttnGradients the blocks' backward fills, or None
 
     def forward(self, x):
         m = self.enc.model
@@ -1206,6 +1332,9 @@ class _VisualRun:
         # goes on through the patch embedding to the pixels
         self.x_grad = (tuple(x.shape), x.dtype) if torch.is_tensor(x) and x.requires_grad else None
         k = tr.frozen_prefix(m.stage_params(), self.x_grad is not None)
+        ag, self.attn_grads = self.attn_grads, None   # (the saved dicts of the chosen blocks carry it to backward)
+        if ag is not None:   # a chosen block must be inside the backward range: the prefix ends in front of the first one
+            k = min(k, 1 + ag.first())
         self.nfro, self.embed_frozen = max(k - 1, 0), k >= 1
         tok, T, W, N = m._embed(x)
         collect, self.collect = self.collect, None   # (nothing of it is needed in backward)
@@ -1225,8 +1354,9 @@ class _VisualRun:
             tok = run_prefix_blocks(m.blocks[:self.nfro], tok, B, T, W, collect=collect)
             for blk in m.blocks[:self.nfro]:
                 blk._presampled = None
-        for blk in m.blocks[self.nfro:]:
-            tok, sv = blk.forward_train(tok, B, T, W, collect=collect.block_begin() if collect is not None else None)
+        for j, blk in enumerate(m.blocks[self.nfro:], self.nfro):
+            tok, sv = blk.forward_train(tok, B, T, W, collect=collect.block_begin() if collect is not None else None,
+                                        attn_grads=(ag, j) if (ag is not None and ag.wants(j)) else None)
             blk._presampled = None
             if collect is not None:   # (the maps are already taken, inside the block: before the saved dict is cut down below)
                 collect.block_end(tok)

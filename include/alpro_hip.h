@@ -651,6 +651,21 @@ int alpro_attn_temporal_probs(const void* qkv, const float* lse, float* out, int
 int alpro_attn_probs_grad(const void* qkv, const void* dctx, const float* lse, const float* key_bias, float* grad_out, float* cam_out, int dtype,
                           int batch, int L, int H, float scale, float grad_scale, int q0, int nq, int k0, int nk, void* stream);
 
+/* ---- gradient of a score w.r.t. the temporal attention probabilities, and their Grad-CAM map (TimeSformer.forward_features attn_grads;
+ * retain_grad() on the input of temporal_attn.attn_drop, vit.py:92-93 on the view of vit.py:147) ----
+ * For group g = rows g*T .. g*T + T - 1, all fp32, (rows / T, H, T, T) contiguous:
+ *   grad_out[g][h][q][k] = grad_scale * <dctx[g*T + q][h*64 .. h*64 + 63], v_(g*T+k, h)>      (d score / d P, P the softmax BEFORE dropout)
+ *   cam_out [g][h][q][k] = P * max(grad, 0), P exactly alpro_attn_temporal_probs' value for the same qkv / lse / scale
+ * qkv, lse, rows, T, H, scale: as for alpro_attn_temporal_probs.  dctx (rows, H*64), dtype of qkv: the gradient w.r.t. the temporal attention
+ * output, what alpro_attn_temporal_bwd takes as d_out.  grad_scale: one fp32 multiply on the 64-term dot product (the caller passes 1 / loss
+ * scale).  Either output may be NULL, not both; a NULL output costs nothing (without cam_out the q / k thirds and lse are not read and the
+ * scores are not formed).  No dropout arguments.  The two forms of alpro_attn_temporal_probs, each with a second accumulator set (v rows
+ * against dctx rows).  16-bit operands use the 16-bit MFMA, fp32 the fp32 MFMA (exact products).  qkv, dctx and both outputs 16-byte
+ * aligned; rows == 0 is a no-op.  Every argument is checked before the first HIP call.  One launch, no LDS, no atomics, no workspace:
+ * bitwise reproducible. */
+int alpro_attn_temporal_probs_grad(const void* qkv, const void* dctx, const float* lse, float* grad_out, float* cam_out, int dtype, int64_t rows,
+                                   int T, int H, float scale, float grad_scale, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
