@@ -214,7 +214,8 @@ extern "C" int alpro_vtc_loss_bwd(const float* v, const float* t, const float* g
                                   int col0, const float* sim_v2t, const float* sim_t2v, const float* lse, const float* dloss, float* ds_v2t,
                                   float* ds_t2v, float* dv, float* dt, float* dgv, float* dgt, float* dtemp, void* stream) {
   ALPRO_CHECK(v && t && gv && gt && temp && sim_v2t && sim_t2v && lse && dloss && ds_v2t && ds_t2v && dv && dt && dgv && dgt, "alpro_vtc_loss_bwd: null argument");
-  ALPRO_CHECK(B > 0 && G >= B && E > 0 && E % 4 == 0 && E <= VTC_MAX_E && G <= 8192, "alpro_vtc_loss_bwd: bad shape B=%d G=%d E=%d", B, G, E);
+  // col0 as the forward checks it: outside [0, G - B] no column is a positive, and the gradients would be those of another loss
+  ALPRO_CHECK(B > 0 && G >= B && E > 0 && E % 4 == 0 && E <= VTC_MAX_E && G <= 8192 && col0 >= 0 && col0 + B <= G, "alpro_vtc_loss_bwd: bad shape B=%d G=%d E=%d col0=%d", B, G, E, col0);
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(vtc_bwd_rows_kernel, dim3(2 * B), dim3(256), G * sizeof(float), st, gv, gt, temp, B, G, E, col0, sim_v2t, sim_t2v, lse, dloss, ds_v2t,
                      ds_t2v, dv, dt);

@@ -536,7 +536,8 @@ int alpro_softmax_xent(const float* logits, int64_t ld, const int64_t* labels, i
  *   sim_v2t = v gt^T / temp, sim_t2v = t gv^T / temp   (B, G) fp32, written out (hard-negative mining :287-306 reads them)
  *   *loss   = (mean_i CE(sim_v2t[i], col0 + i) + mean_i CE(sim_t2v[i], col0 + i)) / 2;  lse (2B): row log-sum-exps for the backward.
  * _bwd: gradients w.r.t. v, t (B, E), gv, gt (G, E) and temp (*dtemp, optional) for upstream *dloss; ds_* are (B, G) scratch.
- * *loss and *dtemp are summed in a fixed order by one finishing workgroup each (ABI 16; before: one fp32 atomic per row) -- bit-reproducible. */
+ * *loss and *dtemp are summed in a fixed order by one finishing workgroup each (ABI 16; before: one fp32 atomic per row) -- bit-reproducible.
+ * Both refuse E % 4 != 0, E > 1024, G < B and col0 outside [0, G - B]; _bwd also G > 8192 (its ds row lives in LDS). */
 int alpro_vtc_loss_fwd(const float* v, const float* t, const float* gv, const float* gt, const float* temp, int B, int G, int E, int col0,
                        float* sim_v2t, float* sim_t2v, float* lse, float* loss, void* stream);
 int alpro_vtc_loss_bwd(const float* v, const float* t, const float* gv, const float* gt, const float* temp, int B, int G, int E, int col0,
