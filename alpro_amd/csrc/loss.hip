@@ -196,6 +196,109 @@ __global__ __launch_bounds__(256) void vtc_bwd_cols_kernel(const float* __restri
     dk[e] = acc * inv_temp;
   }
 }
+
+// ---- the same loss with several positives per row (alpro_vtc_loss_ids_*) ------------------------------------
+// match(i, j) = (j == col0 + i) || (ids[i] >= 0 && gids[j] == ids[i]), n_i = #matches >= 1, target = match / n_i.  The similarities and lse
+// are vtc_fwd_kernel's, d temp and the key gradients vtc_dtemp_kernel's and vtc_bwd_cols_kernel's (they read nothing but ds): the two kernels
+// below stand beside vtc_loss_finish_kernel and vtc_bwd_rows_kernel, which stay as they are.  With n_i = 1 every value below is the plain
+// kernels' bit for bit: the match sum adds zeros to the one positive, 1 / n_i is 1.
+__device__ __forceinline__ int wave_sum_int(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// (no short circuit: gids[j] is loaded whatever the other terms say, so that the loads of a sweep do not wait for one another's comparisons)
+__device__ __forceinline__ bool vtc_match(int j, int own, int64_t id, const int64_t* __restrict__ gids) {
+  const int64_t g = gids[j];
+  return (j == own) | ((id >= 0) & (g == id));
+}
+
+// loss = sum over (direction, row) of (lse - mean of the matching logits) / (2B).  One workgroup, as vtc_loss_finish_kernel, and its order: thread
+// k < 256 adds rows k, k + 256, ... in ascending order, then block_reduce's tree over the first four waves.  The 256 terms of a trip are made by
+// all sixteen waves first (wave w: rows w, w + 16, ... of the trip; lane l adds the matching columns l, l + 64, ... in ascending order, then the
+// butterfly) and handed over in LDS.  The logits are loaded whether they match or not, so that no load waits for a comparison.
+// One workgroup because the entry point has nowhere to keep 2B row terms between two launches: the sweep over 2B x G logits and ids runs on one
+// CU (+14 us over the plain forward at B = 64, G = 512; +153 us at G = 8192; the header states the range in which that is sensible).
+__global__ __launch_bounds__(1024) void vtc_ids_loss_finish_kernel(const float* __restrict__ sim_v2t, const float* __restrict__ sim_t2v,
+                                                                   const float* __restrict__ lse, const int64_t* __restrict__ ids,
+                                                                   const int64_t* __restrict__ gids, int B, int G, int col0, float* __restrict__ loss) {
+  __shared__ float sh[4];
+  __shared__ float terms[256];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  float s = 0.f;
+  for (int k0 = 0; k0 < 2 * B; k0 += 256) {
+    __syncthreads();  // the terms of the trip before are read
+    for (int r = w; r < 256 && k0 + r < 2 * B; r += 16) {
+      const int k = k0 + r, dir = k / B, i = k - dir * B, own = col0 + i;
+      const float* sim = (dir == 0 ? sim_v2t : sim_t2v) + (int64_t)i * G;
+      const int64_t id = ids[i];
+      float m = 0.f;
+      int n = 0;
+      if (id < 0) {  // no id: the own column alone, without the sweep
+        if (lane == 0) m = sim[own], n = 1;
+      } else {
+#pragma unroll 8
+        for (int j = lane; j < G; j += 64) {  // (unrolled: the loads of eight columns are in flight together; the additions keep their order)
+          const bool hit = vtc_match(j, own, id, gids);
+          const float x = sim[j];
+          m += hit ? x : 0.f;
+          n += hit ? 1 : 0;
+        }
+      }
+      m = wave_sum(m);
+      n = wave_sum_int(n);
+      if (lane == 0) terms[r] = lse[k] - __fmul_rn(m, 1.0f / (float)n);  // (no contraction: one rounding for the mean, one for the difference)
+    }
+    __syncthreads();
+    if (threadIdx.x < 256 && k0 + (int)threadIdx.x < 2 * B) s += terms[threadIdx.x];
+  }
+  s = wave_sum(s);
+  if (w < 4 && lane == 0) sh[w] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) *loss = (((sh[0] + sh[1]) + sh[2]) + sh[3]) * (0.5f / B);
+}
+
+// Backward, rows: ds[i][j] = (softmax(sim[i])[j] - match(i, j) / n_i) * dloss / (2B), then vtc_bwd_rows_kernel's chain for d(query i).
+__global__ __launch_bounds__(256) void vtc_ids_bwd_rows_kernel(const float* __restrict__ gv, const float* __restrict__ gt, const float* __restrict__ temp,
+                                                               const int64_t* __restrict__ ids, const int64_t* __restrict__ gids, int B, int G, int E,
+                                                               int col0, const float* __restrict__ sim_v2t, const float* __restrict__ sim_t2v,
+                                                               const float* __restrict__ lse, const float* __restrict__ dloss,
+                                                               float* __restrict__ ds_v2t, float* __restrict__ ds_t2v, float* __restrict__ dv,
+                                                               float* __restrict__ dt) {
+  extern __shared__ float dsrow[];  // G floats
+  __shared__ int cnt[4];
+  const int dir = blockIdx.x / B, i = blockIdx.x - dir * B, own = col0 + i;
+  const float* keys = dir == 0 ? gt : gv;
+  const float* sim = (dir == 0 ? sim_v2t : sim_t2v) + (int64_t)i * G;
+  float* ds = (dir == 0 ? ds_v2t : ds_t2v) + (int64_t)i * G;
+  const int64_t id = ids[i];
+  int n = 1;
+  if (id >= 0) {  // (uniform over the workgroup)
+    n = 0;
+    for (int j = threadIdx.x; j < G; j += 256) n += vtc_match(j, own, id, gids) ? 1 : 0;
+    n = wave_sum_int(n);
+    if ((threadIdx.x & 63) == 0) cnt[threadIdx.x >> 6] = n;
+    __syncthreads();
+    n = cnt[0] + cnt[1] + cnt[2] + cnt[3];
+  }
+  const float target = 1.0f / (float)n;
+  const float tc = fminf(fmaxf(*temp, 0.001f), 0.5f);
+  const float inv_temp = 1.0f / tc;
+  const float scale = *dloss * (0.5f / B), l = lse[blockIdx.x];
+  for (int j = threadIdx.x; j < G; j += 256) {
+    const float d = (expf(sim[j] - l) - (vtc_match(j, own, id, gids) ? target : 0.f)) * scale;
+    dsrow[j] = d;
+    ds[j] = d;
+  }
+  __syncthreads();  // publishes dsrow
+  float* dq = (dir == 0 ? dv : dt) + (int64_t)i * E;
+  for (int e = threadIdx.x; e < E; e += 256) {
+    float acc = 0.f;
+    for (int j = 0; j < G; ++j) acc = fmaf(dsrow[j], keys[(int64_t)j * E + e], acc);
+    dq[e] = acc * inv_temp;
+  }
+}
 }  // namespace
 }  // namespace alpro
 
@@ -222,6 +325,31 @@ extern "C" int alpro_vtc_loss_bwd(const float* v, const float* t, const float* g
   if (dtemp) hipLaunchKernelGGL(vtc_dtemp_kernel, dim3(1), dim3(1024), 0, st, temp, sim_v2t, sim_t2v, ds_v2t, ds_t2v, (int64_t)B * G, dtemp);
   hipLaunchKernelGGL(vtc_bwd_cols_kernel, dim3(2 * G), dim3(256), 0, st, v, t, temp, B, G, E, ds_v2t, ds_t2v, dgv, dgt);
   return check_launch("alpro_vtc_loss_bwd");
+}
+
+extern "C" int alpro_vtc_loss_ids_fwd(const float* v, const float* t, const float* gv, const float* gt, const float* temp, const int64_t* ids,
+                                      const int64_t* gids, int B, int G, int E, int col0, float* sim_v2t, float* sim_t2v, float* lse, float* loss,
+                                      void* stream) {
+  ALPRO_CHECK(v && t && gv && gt && temp && ids && gids && sim_v2t && sim_t2v && lse && loss, "alpro_vtc_loss_ids_fwd: null argument");
+  ALPRO_CHECK(B > 0 && G >= B && E > 0 && E % 4 == 0 && E <= VTC_MAX_E && col0 >= 0 && col0 + B <= G, "alpro_vtc_loss_ids_fwd: bad shape B=%d G=%d E=%d col0=%d", B, G, E, col0);
+  hipLaunchKernelGGL(vtc_fwd_kernel, dim3(2 * B), dim3(256), 0, (hipStream_t)stream, v, t, gv, gt, temp, B, G, E, col0, sim_v2t, sim_t2v, lse);
+  hipLaunchKernelGGL(vtc_ids_loss_finish_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, sim_v2t, sim_t2v, lse, ids, gids, B, G, col0, loss);
+  return check_launch("alpro_vtc_loss_ids_fwd");
+}
+
+extern "C" int alpro_vtc_loss_ids_bwd(const float* v, const float* t, const float* gv, const float* gt, const float* temp, const int64_t* ids,
+                                      const int64_t* gids, int B, int G, int E, int col0, const float* sim_v2t, const float* sim_t2v,
+                                      const float* lse, const float* dloss, float* ds_v2t, float* ds_t2v, float* dv, float* dt, float* dgv,
+                                      float* dgt, float* dtemp, void* stream) {
+  ALPRO_CHECK(v && t && gv && gt && temp && ids && gids && sim_v2t && sim_t2v && lse && dloss && ds_v2t && ds_t2v && dv && dt && dgv && dgt,
+              "alpro_vtc_loss_ids_bwd: null argument");
+  ALPRO_CHECK(B > 0 && G >= B && E > 0 && E % 4 == 0 && E <= VTC_MAX_E && G <= 8192 && col0 >= 0 && col0 + B <= G, "alpro_vtc_loss_ids_bwd: bad shape B=%d G=%d E=%d col0=%d", B, G, E, col0);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(vtc_ids_bwd_rows_kernel, dim3(2 * B), dim3(256), G * sizeof(float), st, gv, gt, temp, ids, gids, B, G, E, col0, sim_v2t, sim_t2v, lse,
+                     dloss, ds_v2t, ds_t2v, dv, dt);
+  if (dtemp) hipLaunchKernelGGL(vtc_dtemp_kernel, dim3(1), dim3(1024), 0, st, temp, sim_v2t, sim_t2v, ds_v2t, ds_t2v, (int64_t)B * G, dtemp);
+  hipLaunchKernelGGL(vtc_bwd_cols_kernel, dim3(2 * G), dim3(256), 0, st, v, t, temp, B, G, E, ds_v2t, ds_t2v, dgv, dgt);
+  return check_launch("alpro_vtc_loss_ids_bwd");
 }
 
 extern "C" int alpro_softmax_xent(const float* logits, int64_t ld, const int64_t* labels, int ignore_index, float* loss_rows, void* dlogits,

@@ -138,7 +138,9 @@ class _AllGather(torch.autograd.Function):
 
 
 def allgather(x, name=None):
-    """Concatenate x from every rank along dim 0, in rank order; gradient flows back (alpro_models.py:110-111)."""
+    """Concatenate x from every rank along dim 0, in rank order; gradient flows back (alpro_models.py:110-111).  An integer tensor (the pairs'
+    video ids) goes the same way: it cannot ask for a gradient, so _AllGather.apply returns a tensor without grad_fn and the reduce-scatter
+    backward is never reached (tests/test_vtc_ids_cpu.py holds it to that)."""
     if not collectives_active():
         return x
     return _AllGather.apply(x)

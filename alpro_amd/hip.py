@@ -34,7 +34,8 @@ EXPORTS = ["alpro_hip_last_error", "alpro_hip_abi_version", "alpro_hip_set_optio
            "alpro_hip_sched_workspace_bytes", "alpro_hip_set_sched_workspace", "alpro_hip_release_stream", "alpro_gemm_qkv_tattn", "alpro_add_layernorm_pre_mlp2", "alpro_adamw_step_lp",
            "alpro_gemm_rows_f32_relu_mask", "alpro_clip_pool", "alpro_adamw_step_groups", "alpro_attn_temporal_fwd_drop", "alpro_attn_temporal_bwd_drop",
            "alpro_vit_final_pool_mode", "alpro_vit_final_pool_mode_bwd", "alpro_augment_stage", "alpro_augment_stats", "alpro_resized_crop",
-           "alpro_sim_topk", "alpro_sim_topk_workspace_bytes", "alpro_attn_probs", "alpro_attn_temporal_probs", "alpro_attn_probs_grad", "alpro_unpatchify", "alpro_attn_temporal_probs_grad"]
+           "alpro_sim_topk", "alpro_sim_topk_workspace_bytes", "alpro_attn_probs", "alpro_attn_temporal_probs", "alpro_attn_probs_grad", "alpro_unpatchify", "alpro_attn_temporal_probs_grad",
+           "alpro_vtc_loss_ids_fwd", "alpro_vtc_loss_ids_bwd"]
 
 
 class GemmDesc(ctypes.Structure):
@@ -164,6 +165,8 @@ def load():
     lib.alpro_resized_crop.argtypes = [vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, vp]
     lib.alpro_vtc_loss_fwd.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
     lib.alpro_vtc_loss_bwd.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.alpro_vtc_loss_ids_fwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
+    lib.alpro_vtc_loss_ids_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.alpro_sim_topk_workspace_bytes.argtypes = [i32, i32, i32, i32]
     lib.alpro_sim_topk_workspace_bytes.restype = ctypes.c_size_t
     lib.alpro_sim_topk.argtypes = [vp, i32, vp, i32, i32, i32, f32, i32, vp, vp, vp, ctypes.c_size_t, vp]
@@ -1286,6 +1289,51 @@ def vtc_loss_bwd(v, t, gv, gt, temp, col0, sim_v2t, sim_t2v, lse, dloss, want_dt
     _check(lib.alpro_vtc_loss_bwd(_ptr(v), _ptr(t), _ptr(gv), _ptr(gt), _ptr(temp), B, G, E, int(col0), _ptr(sim_v2t), _ptr(sim_t2v), _ptr(lse),
                                   _ptr(dloss), _ptr(ds[0]), _ptr(ds[1]), _ptr(dv), _ptr(dt), _ptr(dgv), _ptr(dgt), _ptr(dtemp), _stream()),
            "alpro_vtc_loss_bwd")
+    return dv, dt, dgv, dgt, dtemp
+
+
+def _vtc_ids(ids, gids, B, G):
+    for x, n in ((ids, B), (gids, G)):
+        _dev(x, torch.int64)
+        if x.dim() != 1 or x.shape[0] != n or not x.is_contiguous():
+            raise RuntimeError("expected a contiguous int64 id vector of %d elements, got %s" % (n, tuple(x.shape)))
+
+
+def vtc_loss_ids_fwd(v, t, gv, gt, temp, ids, gids, col0):
+    """alpro_vtc_loss_ids_fwd: the contrastive loss with every column of the row's video id a positive (ids (B,), gids (G,) int64; a negative id:
+    the own column alone).  Returns (loss (), sim_v2t (B, G), sim_t2v (B, G), lse (2B,)); the last three are vtc_loss_fwd's bit for bit."""
+    lib = load()
+    for x in (v, t, gv, gt):
+        _dev(x, torch.float32)
+        assert x.is_contiguous()
+    _dev(temp, torch.float32)
+    B, E = v.shape
+    G = gv.shape[0]
+    _vtc_ids(ids, gids, B, G)
+    sim_v2t = torch.empty((B, G), dtype=torch.float32, device=v.device)
+    sim_t2v = torch.empty_like(sim_v2t)
+    lse = torch.empty(2 * B, dtype=torch.float32, device=v.device)
+    loss = torch.empty((), dtype=torch.float32, device=v.device)
+    _check(lib.alpro_vtc_loss_ids_fwd(_ptr(v), _ptr(t), _ptr(gv), _ptr(gt), _ptr(temp), _ptr(ids), _ptr(gids), B, G, E, int(col0), _ptr(sim_v2t),
+                                      _ptr(sim_t2v), _ptr(lse), _ptr(loss), _stream()), "alpro_vtc_loss_ids_fwd")
+    return loss, sim_v2t, sim_t2v, lse
+
+
+def vtc_loss_ids_bwd(v, t, gv, gt, temp, ids, gids, col0, sim_v2t, sim_t2v, lse, dloss, want_dtemp=True):
+    """alpro_vtc_loss_ids_bwd: returns (dv, dt, dgv, dgt, dtemp or None)."""
+    lib = load()
+    B, E = v.shape
+    G = gv.shape[0]
+    _vtc_ids(ids, gids, B, G)
+    dev = v.device
+    ds = torch.empty((2, B, G), dtype=torch.float32, device=dev)
+    dv, dt = torch.empty_like(v), torch.empty_like(t)
+    dgv, dgt = torch.empty_like(gv), torch.empty_like(gt)
+    dtemp = torch.empty((), dtype=torch.float32, device=dev) if want_dtemp else None
+    dloss = dloss.reshape(()).to(torch.float32).contiguous()
+    _check(lib.alpro_vtc_loss_ids_bwd(_ptr(v), _ptr(t), _ptr(gv), _ptr(gt), _ptr(temp), _ptr(ids), _ptr(gids), B, G, E, int(col0), _ptr(sim_v2t),
+                                      _ptr(sim_t2v), _ptr(lse), _ptr(dloss), _ptr(ds[0]), _ptr(ds[1]), _ptr(dv), _ptr(dt), _ptr(dgv), _ptr(dgt),
+                                      _ptr(dtemp), _stream()), "alpro_vtc_loss_ids_bwd")
     return dv, dt, dgv, dgt, dtemp
 
 

@@ -55,6 +55,16 @@ def mask_batch_text_tokens(inputs, mask_token_id, vocab_size, special_token_ids=
     return inputs, labels
 
 
+def video_ids(names, device="cuda"):
+    """List of video names (the collator's vid_id per pair; None: a pair without one, e.g. an image-text pair) -> (B,) int64 for the batch key
+    `video_ids`: the first 8 bytes of blake2b(UTF-8 name), big-endian, masked to 63 bits; None -> -1 ("no id": the pair matches only itself).
+    The same on every rank and in every process (Python's hash() is salted per process), so ids gathered across ranks compare."""
+    import hashlib
+    vals = [-1 if n is None else int.from_bytes(hashlib.blake2b(str(n).encode("utf-8"), digest_size=8).digest(), "big") & ((1 << 63) - 1)
+            for n in names]
+    return torch.tensor(vals, dtype=torch.int64).to(device)
+
+
 def sample_erase_box(img_h, img_w, patch_size, s_l=0.3, s_h=0.5, r_1=0.3, r_2=1 / 0.3, rng=np.random):
     """One patch-aligned rectangle (top, left, h, w) by the reference's rejection sampling."""
     while True:

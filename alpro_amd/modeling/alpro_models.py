@@ -124,6 +124,32 @@ class _VtcLoss(torch.autograd.Function):
         return dv, dt, dgv, dgt, dtemp, None
 
 
+class _VtcLossIds(torch.autograd.Function):
+    """alpro_vtc_loss_ids as an autograd node: _VtcLoss with the pairs' video ids (ids (B,), gathered gids (G,), int64) -- every column that
+    carries the row's id is a positive and the target is uniform over them.  The ids take no gradient."""
+
+    @staticmethod
+    def forward(ctx, v, t, gv, gt, temp, col0, ids, gids):
+        v, t, gv, gt = (x.contiguous().float() for x in (v, t, gv, gt))
+        temp32 = temp.detach().reshape(1).float().contiguous()
+        ids, gids = ids.detach().contiguous(), gids.detach().contiguous()
+        loss, sim_v2t, sim_t2v, lse = hip.vtc_loss_ids_fwd(v, t, gv, gt, temp32, ids, gids, col0)
+        ctx.save_for_backward(v, t, gv, gt, temp32, sim_v2t, sim_t2v, lse, ids, gids)
+        ctx.col0 = col0
+        ctx.mark_non_differentiable(sim_v2t, sim_t2v)
+        ctx.set_materialize_grads(False)
+        return loss, sim_v2t, sim_t2v
+
+    @staticmethod
+    def backward(ctx, dloss, _d1, _d2):
+        if dloss is None:
+            return (None,) * 8
+        v, t, gv, gt, temp32, sim_v2t, sim_t2v, lse, ids, gids = ctx.saved_tensors
+        dv, dt, dgv, dgt, dtemp = hip.vtc_loss_ids_bwd(v, t, gv, gt, temp32, ids, gids, ctx.col0, sim_v2t, sim_t2v, lse, dloss,
+                                                       want_dtemp=ctx.needs_input_grad[4])
+        return dv, dt, dgv, dgt, dtemp, None, None, None
+
+
 class AlproBaseModel(nn.Module):
     def __init__(self, config=None, input_format='RGB', video_enc_cfg=None, temp=0.07):
         super().__init__()
@@ -162,13 +188,19 @@ class AlproBaseModel(nn.Module):
     def _text_feat(self, text_embeds):
         return F.normalize(_linear32(text_embeds[:, 0, :], self.text_proj), dim=-1)
 
-    def _vtc(self, video_feat, text_feat):
-        """In-batch video-text contrastive loss over the gathered features (alpro_models.py:109-128)."""
+    def _vtc(self, video_feat, text_feat, ids=None):
+        """In-batch video-text contrastive loss over the gathered features (alpro_models.py:109-128).  ids: the batch key `video_ids`, (B,) int64
+        -- every gathered pair of the row's video is then a positive (the reference's FIXME, dataset_video_retrieval.py:101)."""
         b = video_feat.shape[0]
         gathered_video_feats = hvd.allgather(video_feat)
         gathered_text_feats = hvd.allgather(text_feat)
         b_start = b * hvd.local_rank()   # targets: eye(b) at columns [b_start, b_start + b) of the gathered similarity (:121-123)
-        loss, sim_v2t, sim_t2v = _VtcLoss.apply(video_feat, text_feat, gathered_video_feats, gathered_text_feats, self.temp, b_start)
+        if ids is None:
+            loss, sim_v2t, sim_t2v = _VtcLoss.apply(video_feat, text_feat, gathered_video_feats, gathered_text_feats, self.temp, b_start)
+        else:
+            ids = ids.to(device=video_feat.device, dtype=torch.long).reshape(b)
+            loss, sim_v2t, sim_t2v = _VtcLossIds.apply(video_feat, text_feat, gathered_video_feats, gathered_text_feats, self.temp, b_start,
+                                                       ids, hvd.allgather(ids))
         return loss, sim_v2t, sim_t2v, b_start
 
     @staticmethod
@@ -188,13 +220,36 @@ class AlproBaseModel(nn.Module):
             neg_text = torch.multinomial(weights_v2t, 1).view(-1)   # a negative text for each video
         return neg_video, neg_text
 
-    def _vtm(self, text_embeds, text_atts, video_embeds, video_atts, sim_v2t, sim_t2v, cls_only=False):
+    @staticmethod
+    def _sample_negatives_ids(sim_v2t, sim_t2v, bs, ids):
+        """_sample_negatives where no pair of the row's own video can be drawn: the columns whose id equals the row's (ids (bs,) int64; a negative
+        id equals nothing) are masked beside the diagonal.  A row that would lose every column (all local pairs from one video) keeps the
+        diagonal-only mask.  With distinct ids the weights, and so the draws under one seed, are _sample_negatives'."""
+        local_rank = hvd.local_rank()
+        b_start, b_end = bs * local_rank, bs * (local_rank + 1)
+        with torch.no_grad():
+            ids = ids.reshape(bs).to(sim_v2t.device)
+            eye = torch.eye(bs, dtype=torch.bool, device=ids.device)
+            same = ((ids[:, None] == ids[None, :]) & (ids[:, None] >= 0)) | eye
+            mask = torch.where(same.all(dim=1, keepdim=True), eye, same)
+            weights_v2t = sim_v2t[:, b_start:b_end].detach().masked_fill(mask, -np.inf)
+            weights_t2v = sim_t2v[:, b_start:b_end].detach().masked_fill(mask, -np.inf)
+            weights_v2t = F.softmax(weights_v2t, dim=1)
+            weights_t2v = F.softmax(weights_t2v, dim=1)
+            neg_video = torch.multinomial(weights_t2v, 1).view(-1)  # a negative video for each text
+            neg_text = torch.multinomial(weights_v2t, 1).view(-1)   # a negative text for each video
+        return neg_video, neg_text
+
+    def _vtm(self, text_embeds, text_atts, video_embeds, video_atts, sim_v2t, sim_t2v, cls_only=False, ids=None):
         """Video-text matching with in-batch hard negatives (alpro_models.py:269-344 / 800-872).
         cls_only: the caller reads nothing but the ITM logits (the retrieval model, alpro_models.py:800-872) -- the last fusion layer's row-wise tail then
         runs on the 3B [CLS] rows alone (BertLayer.forward_train rows=...; ALPRO_FUSION_TAIL_ROWS=0: every row) and `pos` is not returned."""
         device = text_embeds.device
         bs = text_embeds.shape[0]
-        neg_video, neg_text = self._sample_negatives(sim_v2t, sim_t2v, bs)
+        if ids is None:
+            neg_video, neg_text = self._sample_negatives(sim_v2t, sim_t2v, bs)
+        else:
+            neg_video, neg_text = self._sample_negatives_ids(sim_v2t, sim_t2v, bs, ids)
         # positives and the 2B negatives as ONE 3B-sequence fusion batch (the reference makes two calls, :278 and :325; the
         # rows are independent, so the results are the same and the GEMM tiles are fuller)
         text_embeds_all = torch.cat([text_embeds, text_embeds, text_embeds[neg_text]], dim=0)
@@ -259,6 +314,7 @@ class AlproForPretrain(AlproBaseModel):
         use_mpm = 'mpm_mask' in batch
         device = visual_inputs.device
         b = visual_inputs.shape[0]
+        ids = batch.get('video_ids')   # optional (B,) int64: pairs of one video are positives of each other and never each other's hard negatives
         batched = 'mlm_labels' in batch and self.batch_encoder_passes
         from alpro_amd import config as rt
         text_side = rt.text_side_stream(device) if batched else None
@@ -299,8 +355,12 @@ class AlproForPretrain(AlproBaseModel):
                 torch.cuda.current_stream(device).wait_stream(text_side)
                 both.record_stream(torch.cuda.current_stream(device))   # allocated on the side stream, read (and possibly outlived) on this one
             text_feat = self._text_feat(both[:b])
-            vtc_loss, sim_v2t, sim_t2v, _ = self._vtc(video_feat, text_feat)
-            neg_video, neg_text = self._sample_negatives(sim_v2t, sim_t2v, b)
+            if ids is None:
+                vtc_loss, sim_v2t, sim_t2v, _ = self._vtc(video_feat, text_feat)
+                neg_video, neg_text = self._sample_negatives(sim_v2t, sim_t2v, b)
+            else:
+                vtc_loss, sim_v2t, sim_t2v, _ = self._vtc(video_feat, text_feat, ids=ids)
+                neg_video, neg_text = self._sample_negatives_ids(sim_v2t, sim_t2v, b, ids)
             ta_all = torch.cat([text_atts, text_atts, text_atts[neg_text], text_atts], dim=0)
             va_all = torch.cat([video_atts] * 4, dim=0)
             # sequence s of the 4B fusion batch = [text pool row ti[s] ; video pool row vi[s]] over the pools (both = [captions ; masked captions],
@@ -334,8 +394,12 @@ class AlproForPretrain(AlproBaseModel):
         else:
             text_embeds = self._text_embeds(batch['text_input_ids'], text_atts)
             text_feat = self._text_feat(text_embeds)
-            vtc_loss, sim_v2t, sim_t2v, _ = self._vtc(video_feat, text_feat)
-            vtm_loss, vtm_logits, vtm_labels, encoder_outputs_pos = self._vtm(text_embeds, text_atts, video_embeds, video_atts, sim_v2t, sim_t2v)
+            if ids is None:
+                vtc_loss, sim_v2t, sim_t2v, _ = self._vtc(video_feat, text_feat)
+                vtm_loss, vtm_logits, vtm_labels, encoder_outputs_pos = self._vtm(text_embeds, text_atts, video_embeds, video_atts, sim_v2t, sim_t2v)
+            else:
+                vtc_loss, sim_v2t, sim_t2v, _ = self._vtc(video_feat, text_feat, ids=ids)
+                vtm_loss, vtm_logits, vtm_labels, encoder_outputs_pos = self._vtm(text_embeds, text_atts, video_embeds, video_atts, sim_v2t, sim_t2v, ids=ids)
             if 'mlm_labels' in batch:
                 mlm_loss, mlm_logits, mlm_labels = self.compute_mlm(batch['mlm_text_input_ids'], text_atts, video_embeds, video_atts, batch['mlm_labels'])
             else:
@@ -460,7 +524,8 @@ class Prompter(AlproBaseModel):
 
     def forward(self, batch):
         _, video_feat, _, text_feat = self.forward_feats(batch)
-        vtc_loss, sim_v2t, sim_t2v, b_start = self._vtc(video_feat, text_feat)
+        ids = batch.get('video_ids')
+        vtc_loss, sim_v2t, sim_t2v, b_start = self._vtc(video_feat, text_feat) if ids is None else self._vtc(video_feat, text_feat, ids=ids)
         itc_labels = b_start + torch.arange(video_feat.shape[0], device=sim_v2t.device)   # == max(sim_targets, 1)[1] (:589)
         return dict(itc_loss=vtc_loss, itc_labels=itc_labels,
                     i2t_scores=F.log_softmax(sim_v2t, dim=1), t2i_scores=F.log_softmax(sim_t2v, dim=1))
@@ -479,8 +544,13 @@ class AlproForVideoTextRetrieval(AlproBaseModel):
         video_atts = torch.ones(video_embeds.size()[:-1], dtype=torch.long, device=visual_inputs.device)
         text_embeds = self._text_embeds(batch['text_input_ids'], text_atts)
         text_feat = self._text_feat(text_embeds)
-        vtc_loss, sim_v2t, sim_t2v, _ = self._vtc(video_feat, text_feat)
-        vtm_loss, vtm_logits, vtm_labels, _ = self._vtm(text_embeds, text_atts, video_embeds, video_atts, sim_v2t, sim_t2v, cls_only=True)
+        ids = batch.get('video_ids')   # optional (B,) int64, see AlproForPretrain.forward
+        if ids is None:
+            vtc_loss, sim_v2t, sim_t2v, _ = self._vtc(video_feat, text_feat)
+            vtm_loss, vtm_logits, vtm_labels, _ = self._vtm(text_embeds, text_atts, video_embeds, video_atts, sim_v2t, sim_t2v, cls_only=True)
+        else:
+            vtc_loss, sim_v2t, sim_t2v, _ = self._vtc(video_feat, text_feat, ids=ids)
+            vtm_loss, vtm_logits, vtm_labels, _ = self._vtm(text_embeds, text_atts, video_embeds, video_atts, sim_v2t, sim_t2v, cls_only=True, ids=ids)
         return dict(itm_scores=vtm_logits, itm_loss=vtm_loss, itm_labels=vtm_labels, itc_loss=vtc_loss)
 
     def compute_vtm(self, text_embeds, text_atts, image_embeds, image_atts, sim_i2t, sim_t2i):

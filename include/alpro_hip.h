@@ -537,12 +537,32 @@ int alpro_softmax_xent(const float* logits, int64_t ld, const int64_t* labels, i
  *   *loss   = (mean_i CE(sim_v2t[i], col0 + i) + mean_i CE(sim_t2v[i], col0 + i)) / 2;  lse (2B): row log-sum-exps for the backward.
  * _bwd: gradients w.r.t. v, t (B, E), gv, gt (G, E) and temp (*dtemp, optional) for upstream *dloss; ds_* are (B, G) scratch.
  * *loss and *dtemp are summed in a fixed order by one finishing workgroup each (ABI 16; before: one fp32 atomic per row) -- bit-reproducible.
- * Both refuse E % 4 != 0, E > 1024, G < B and col0 outside [0, G - B]; _bwd also G > 8192 (its ds row lives in LDS). */
+ * Both refuse E % 4 != 0, E > 1024, G < B and col0 outside [0, G - B]; _bwd also G > 8192 (its ds row lives in LDS).
+ *
+ * _ids_fwd / _ids_bwd: the same loss where a row may have several positives (two captions of one video in a batch; ALBEF's and BLIP's
+ * `idx`).  ids (B) and gids (G) int64 are the pairs' video ids, this rank's and the gathered ones:
+ *   match(i, j) = (j == col0 + i) || (ids[i] >= 0 && gids[j] == ids[i])   (64-bit compare; a negative id is "no id": the own column alone;
+ *                                                                           the own column counts whatever gids[col0 + i] says)
+ *   n_i = #{j : match(i, j)} >= 1;  row_i = lse_i - (sum_{match} sim_ij) / n_i;  *loss = sum over both directions and rows of row_i / (2B)
+ *   ds_ij = (exp(sim_ij - lse_i) - match(i, j) / n_i) * dloss / (2B); dv, dt, dgv, dgt, *dtemp from ds as in _bwd.
+ * sim_*, lse are _fwd's bit for bit whatever the ids; with pairwise distinct non-negative ids or all ids negative (n_i = 1) every output
+ * is _fwd's / _bwd's bit for bit.  Fixed summation order, no atomics.  The refusals of _fwd / _bwd, and null ids / gids.
+ * Cost: _ids_fwd has no scratch for the 2B row terms, so ONE workgroup makes them all (a sweep over 2B x G logits and ids) before it adds them in
+ * the fixed order; that part grows with B * G on one CU.  Measured on an MI355X, forward alone, over _fwd's time: +14 us (34 against 20) at
+ * (B, G) = (64, 512), +41 us (109 / 68) at (64, 2048), +153 us (415 / 262) at (64, 8192), +633 us (1096 / 463) at (512, 4096), E = 256.  Sensible up
+ * to about B * G = 5e5; the forward accepts more (as _fwd, it sets no limit on G) and then spends most of its time there. */
 int alpro_vtc_loss_fwd(const float* v, const float* t, const float* gv, const float* gt, const float* temp, int B, int G, int E, int col0,
                        float* sim_v2t, float* sim_t2v, float* lse, float* loss, void* stream);
 int alpro_vtc_loss_bwd(const float* v, const float* t, const float* gv, const float* gt, const float* temp, int B, int G, int E, int col0,
                        const float* sim_v2t, const float* sim_t2v, const float* lse, const float* dloss, float* ds_v2t, float* ds_t2v,
                        float* dv, float* dt, float* dgv, float* dgt, float* dtemp, void* stream);
+int alpro_vtc_loss_ids_fwd(const float* v, const float* t, const float* gv, const float* gt, const float* temp, const int64_t* ids,
+                           const int64_t* gids, int B, int G, int E, int col0, float* sim_v2t, float* sim_t2v, float* lse, float* loss,
+                           void* stream);
+int alpro_vtc_loss_ids_bwd(const float* v, const float* t, const float* gv, const float* gt, const float* temp, const int64_t* ids,
+                           const int64_t* gids, int B, int G, int E, int col0, const float* sim_v2t, const float* sim_t2v, const float* lse,
+                           const float* dloss, float* ds_v2t, float* ds_t2v, float* dv, float* dt, float* dgv, float* dgt, float* dtemp,
+                           void* stream);
 
 /* ---- step epilogue on flat fp32 buffers (run_pretrain_sparse.py:633-648, src/optimization/adamw.py:40-103) ---- */
 
