@@ -3,7 +3,7 @@
 // The reference stacks the clips' logits on the host and pools there; here it is one launch over the device logits, and one host copy of the
 // (B,) answers follows.  One workgroup per question: each thread pools its columns over the C clips in clip order, then a fixed-shape tree
 // (wave shuffles, then 4 wave results through LDS) finds the argmax.  Memory-bound (B*C*A floats read once), no atomics: bitwise reproducible.
-#include "common.hpp"
+#include "clip_pool.hpp"
 
 namespace alpro {
 namespace {
@@ -24,22 +24,7 @@ __global__ __launch_bounds__(256) void clip_pool_kernel(const float* __restrict_
   float best = -INFINITY;
   int best_i = A;   // past every column: loses to any real one
   for (int j = tid; j < A; j += 256) {
-    float r;
-    if (MODE == ALPRO_POOL_MEAN) {
-      float s = 0.f;
-      for (int c = 0; c < C; ++c) s += x[(int64_t)c * ld + j];
-      r = s / (float)C;
-    } else {
-      float m = x[j];
-      for (int c = 1; c < C; ++c) m = fmaxf(m, x[(int64_t)c * ld + j]);
-      if (MODE == ALPRO_POOL_MAX || m == -INFINITY || m == INFINITY) {
-        r = m;   // lse: all clips -inf -> -inf (torch.logsumexp); an +inf clip -> +inf
-      } else {
-        float s = 0.f;
-        for (int c = 0; c < C; ++c) s += expf(x[(int64_t)c * ld + j] - m);
-        r = m + logf(s);
-      }
-    }
+    const float r = clip_pool_value<MODE>(C, [&](int c) { return x[(int64_t)c * ld + j]; });
     out[j] = r;
     take_better(best, best_i, r, j);   // j grows: a later column wins only on a larger value
   }

@@ -35,7 +35,7 @@ EXPORTS = ["alpro_hip_last_error", "alpro_hip_abi_version", "alpro_hip_set_optio
            "alpro_gemm_rows_f32_relu_mask", "alpro_clip_pool", "alpro_adamw_step_groups", "alpro_attn_temporal_fwd_drop", "alpro_attn_temporal_bwd_drop",
            "alpro_vit_final_pool_mode", "alpro_vit_final_pool_mode_bwd", "alpro_augment_stage", "alpro_augment_stats", "alpro_resized_crop",
            "alpro_sim_topk", "alpro_sim_topk_workspace_bytes", "alpro_attn_probs", "alpro_attn_temporal_probs", "alpro_attn_probs_grad", "alpro_unpatchify", "alpro_attn_temporal_probs_grad",
-           "alpro_vtc_loss_ids_fwd", "alpro_vtc_loss_ids_bwd"]
+           "alpro_vtc_loss_ids_fwd", "alpro_vtc_loss_ids_bwd", "alpro_sim_topk_clips", "alpro_sim_topk_clips_workspace_bytes"]
 
 
 class GemmDesc(ctypes.Structure):
@@ -170,6 +170,9 @@ def load():
     lib.alpro_sim_topk_workspace_bytes.argtypes = [i32, i32, i32, i32]
     lib.alpro_sim_topk_workspace_bytes.restype = ctypes.c_size_t
     lib.alpro_sim_topk.argtypes = [vp, i32, vp, i32, i32, i32, f32, i32, vp, vp, vp, ctypes.c_size_t, vp]
+    lib.alpro_sim_topk_clips_workspace_bytes.argtypes = [i32, i32, i32, i32, i32, i32]
+    lib.alpro_sim_topk_clips_workspace_bytes.restype = ctypes.c_size_t
+    lib.alpro_sim_topk_clips.argtypes = [vp, i32, vp, i32, i32, i32, f32, i32, i32, i32, i32, vp, vp, vp, ctypes.c_size_t, vp]
     lib.alpro_attn_probs.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, i32, i32, i32, vp]
     lib.alpro_attn_temporal_probs.argtypes = [vp, vp, vp, i32, i64, i32, i32, f32, vp]
     lib.alpro_attn_probs_grad.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, i32, i32, i32, i32, vp]
@@ -900,6 +903,44 @@ def sim_topk(q, g, k, scale=1.0, chunk=0):
     val = torch.empty((nq, k), dtype=torch.float32, device=q.device)
     idx = torch.empty((nq, k), dtype=torch.int32, device=q.device)
     _check(lib.alpro_sim_topk(_ptr(q), nq, _ptr(g), ng, d, k, float(scale), chunk, _ptr(val), _ptr(idx), _ptr(ws), need, _stream()), "alpro_sim_topk")
+    return val, idx
+
+
+TOPK_MAX_CLIPS = 32   # ALPRO_TOPK_MAX_CLIPS
+TOPK_CLIPS_SIDES = {"gallery": 0, "query": 1}   # ALPRO_TOPK_CLIPS_GALLERY / _QUERY
+
+
+def sim_topk_clips(q, g, k, clips, side="gallery", mode="mean", scale=1.0, chunk=0):
+    """Top-k by pooled similarity with `clips` clips per video, without a matrix (alpro_sim_topk_clips): q, g (rows, 256) fp32 contiguous; the
+    side that carries the clips has rows v * clips + j.  side 'gallery' (text -> video): g holds the clips -> (values, indices) (nq, k), indices
+    = video indices; side 'query' (video -> text): q holds the clips -> (nq / clips, k), indices = rows of g.  values = the pool (mode 'mean' /
+    'max' / 'lse', hip.clip_pool's arithmetic) over the clips of q . g * scale; each row is ordered by (value descending, index ascending),
+    -inf / -1 behind the gallery.  chunk: gallery entries (videos / rows) per partial pass (0 = the library's choice; the result does not
+    depend on it)."""
+    if mode not in POOL_MODES:
+        raise ValueError("sim_topk_clips: mode %r, expect one of %s" % (mode, sorted(POOL_MODES)))
+    if side not in TOPK_CLIPS_SIDES:
+        raise ValueError("sim_topk_clips: side %r, expect one of %s" % (side, sorted(TOPK_CLIPS_SIDES)))
+    lib = load()
+    for name, t in (("q", q), ("g", g)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError("sim_topk_clips: %s must be a device tensor (got %s): the hot path has no CPU fallback" % (name, getattr(t, "device", type(t))))
+        if t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous():
+            raise RuntimeError("sim_topk_clips: %s must be a contiguous 2-D fp32 tensor (got %s %s, strides %s)" % (name, t.dtype, tuple(t.shape), tuple(t.stride())))
+    if q.shape[1] != g.shape[1] or q.device != g.device:
+        raise RuntimeError("sim_topk_clips: q %s and g %s must share the feature width and the device" % (tuple(q.shape), tuple(g.shape)))
+    nq, ng, d, k, clips, chunk, side = q.shape[0], g.shape[0], q.shape[1], int(k), int(clips), int(chunk), TOPK_CLIPS_SIDES[side]
+    if d != 256:
+        raise RuntimeError("sim_topk_clips: d=%d (the kernel is built for the model's embed_dim, 256)" % d)
+    need = int(lib.alpro_sim_topk_clips_workspace_bytes(nq, ng, k, clips, side, chunk))
+    if need == 0:
+        raise RuntimeError("alpro_sim_topk_clips_workspace_bytes refused the arguments: %s" % lib.alpro_hip_last_error().decode())
+    rows = nq // clips if side == 1 else nq
+    ws = torch.empty(need, dtype=torch.uint8, device=q.device)   # (the caching allocator hands out 512-byte aligned blocks)
+    val = torch.empty((rows, k), dtype=torch.float32, device=q.device)
+    idx = torch.empty((rows, k), dtype=torch.int32, device=q.device)
+    _check(lib.alpro_sim_topk_clips(_ptr(q), nq, _ptr(g), ng, d, k, float(scale), clips, side, POOL_MODES[mode], chunk, _ptr(val), _ptr(idx), _ptr(ws),
+                                    need, _stream()), "alpro_sim_topk_clips")
     return val, idx
 
 

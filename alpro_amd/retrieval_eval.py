@@ -7,6 +7,12 @@ with mini-batches of b captions the reference runs the ViT V*ceil(C/b) times and
 
 Beside the reference's all-pairs evaluation: a two-stage search over the same cached features (rerank_retrieval / rerank_metrics: the k best
 candidates per query by the contrastive features through hip.sim_topk, fusion + ITM on those only), for galleries where V*C passes are too many.
+
+Several clips per video (the reference's inference_n_clips / score_agg_func, config.py:99,190): visual_inputs carries num_clips * num_frm frames,
+clip j of a video is scored like a video of its own -- x_j = its ITC similarity / temp, l_j = its two ITM logits -- and both are pooled
+elementwise over j by mean / max / lse with the rule of run_video_qa.py:269-279 (hip.clip_pool); score = softmax(pooled logits)[1], sim =
+pooled x.  The reference's retrieval loop collects the per-clip logits (run_video_retrieval.py:663-675) and then squeezes the clip axis, which
+only works for one clip; its QA loop still has the pooling, and that is the definition here.  With one clip every function does what it did.
 """
 import math
 from collections import defaultdict
@@ -14,12 +20,31 @@ from collections import defaultdict
 import numpy as np
 import torch
 
+SCORE_AGG_FUNCS = ("mean", "max", "lse")   # hip.POOL_MODES (run_video_qa.py:259-268)
+
+
+def _check_clips(num_clips, score_agg_func):
+    if score_agg_func not in SCORE_AGG_FUNCS:   # qa_eval.inference_qa's text (run_video_qa.py:279)
+        raise ValueError("Invalid value for pool_method, got %s, expect one of [`mean`, `max`, `lse`]" % score_agg_func)
+    if int(num_clips) < 1:
+        raise ValueError("num_clips=%r clips per video (need >= 1)" % (num_clips,))
+
+
+def _pool_clips(x, num_clips, score_agg_func):
+    """x (G * num_clips, A), rows group-major (g * num_clips + j) -> (G, A) fp32 pooled over j by hip.clip_pool; one clip: x itself, untouched"""
+    if num_clips == 1:
+        return x.float()
+    from alpro_amd import hip
+    return hip.clip_pool(x.float().contiguous(), num_clips, score_agg_func)[0]
+
 
 @torch.no_grad()
-def inference_retrieval_cached(model, videos, text_input_ids, text_input_mask, caption_ids, eval_bsz=64, num_clips=1):
+def inference_retrieval_cached(model, videos, text_input_ids, text_input_mask, caption_ids, eval_bsz=64, num_clips=1, score_agg_func="mean"):
     """videos: iterable of (vid_id, visual_inputs (1, num_clips*num_frm, C, H, W)); the captions are shared by all videos
     (each reference batch carries one video and all captions).  Returns the reference's list of
-    dict(vid_id, txt_id, score, sim): score = softmax(itm logits)[:, 1], sim = ITC similarity, both rounded to 4 decimals."""
+    dict(vid_id, txt_id, score, sim): score = softmax(itm logits)[:, 1], sim = ITC similarity, both rounded to 4 decimals; with
+    num_clips > 1 the logits and the similarities are pooled over the clips by score_agg_func first (module docstring)."""
+    _check_clips(num_clips, score_agg_func)
     model.eval()
     n = text_input_ids.shape[0]
     text_cache = []
@@ -30,60 +55,65 @@ def inference_retrieval_cached(model, videos, text_input_ids, text_input_mask, c
     res = []
     for vid_id, visual_inputs in videos:
         T = visual_inputs.shape[1] // num_clips
-        clips = visual_inputs.view((1, num_clips, T) + tuple(visual_inputs.shape[2:]))
-        if num_clips != 1:
-            raise NotImplementedError("the reference's score aggregation is only defined for inference_n_clips == 1 "
-                                      "(run_video_retrieval.py:672-681 squeezes the clip axis)")
-        ve, vf = model.encode_video(clips[:, 0])
+        ve, vf = model.encode_video(visual_inputs.view((num_clips, T) + tuple(visual_inputs.shape[2:])))   # the clips as a batch: (n, 1+N, D), (n, 256)
         for emb, feat, mask, cids in text_cache:
-            out = model.score_pairs(ve, vf, emb, feat, mask)
-            probs = torch.softmax(out["logits"].float(), dim=1)[:, 1].tolist()
-            sims = out["itc_scores"].float().reshape(-1).tolist()
+            outs = [model.score_pairs(ve[j:j + 1], vf[j:j + 1], emb, feat, mask) for j in range(num_clips)]   # one pass per clip, as the reference's loop
+            logits = torch.stack([o["logits"].float() for o in outs], dim=1).reshape(-1, 2)                    # rows caption-major: c * n + j
+            probs = torch.softmax(_pool_clips(logits, num_clips, score_agg_func), dim=1)[:, 1].tolist()
+            sims = _pool_clips(torch.cat([o["itc_scores"].float().reshape(1, -1) for o in outs], 0), num_clips, score_agg_func).reshape(-1).tolist()
             for cid, sc, sim in zip(cids, probs, sims):
                 res.append(dict(vid_id=vid_id, txt_id=cid, score=round(sc, 4), sim=round(sim, 4)))
     return res
 
 
+def _split_clips(videos, num_clips):
+    """(V, n*T, C, H, W), or an iterable of (1, n*T, C, H, W), -> the clips as a batch (V*n, T, C, H, W), row v * n + j"""
+    v = videos if torch.is_tensor(videos) else torch.cat(list(videos), 0)
+    if num_clips == 1:
+        return v
+    if v.shape[1] % num_clips:
+        raise ValueError("visual_inputs carries %d frames per video: not a whole number of num_clips=%d clips" % (v.shape[1], num_clips))
+    return v.reshape((v.shape[0] * num_clips, v.shape[1] // num_clips) + tuple(v.shape[2:]))
+
+
 @torch.no_grad()
-def score_all_pairs(model, videos, text_input_ids, text_input_mask, pair_bsz=512, text_bsz=1024):
+def score_all_pairs(model, videos, text_input_ids, text_input_mask, pair_bsz=512, text_bsz=1024, num_clips=1, score_agg_func="mean"):
     """Every caption against every video with nothing leaving the device: videos (V, T, C, H, W) or an iterable of (1, T, C, H, W)
     clips, captions (C, Lt).  Each video / caption is encoded ONCE; the V*C fusion passes run in flat mini-batches of `pair_bsz`
     (video, caption) pairs gathered from the two caches -- the GEMMs see M = pair_bsz * 237 rows whatever V and C are, where the
     reference loop (run_video_retrieval.py:642-690) runs one video x eval_bsz captions at a time.
+    num_clips = n > 1: videos (V, n*T, ...); the fusion passes run over the (pair, clip) sequences, pair_bsz SEQUENCES at a time (whole
+    pairs: max(1, pair_bsz // n) of them), the logits are pooled over the clips (rows pair-major) and the (V*n, C) similarities likewise,
+    both by hip.clip_pool (module docstring).
     Returns (score (V, C) = softmax(itm_logits)[:, 1], sim (V, C) = ITC similarity), fp32 device tensors (unrounded)."""
-    model.eval()
-    ve, vf = [], []
-    clips = videos if torch.is_tensor(videos) else torch.cat(list(videos), 0)
-    for i in range(0, clips.shape[0], 8):
-        e, f = model.encode_video(clips[i:i + 8])
-        ve.append(e)
-        vf.append(f)
-    ve, vf = torch.cat(ve, 0), torch.cat(vf, 0)                                     # (V, 1+N, D), (V, 256)
-    te, tf = [], []
-    for i in range(0, text_input_ids.shape[0], text_bsz):
-        e, f = model.encode_text(text_input_ids[i:i + text_bsz], text_input_mask[i:i + text_bsz])
-        te.append(e)
-        tf.append(f)
-    te, tf = torch.cat(te, 0), torch.cat(tf, 0)                                     # (C, Lt, D), (C, 256)
-    V, C = ve.shape[0], te.shape[0]
-    sim = vf @ tf.t() / model.temp
+    _check_clips(num_clips, score_agg_func)
+    from alpro_amd.modeling.alpro_models import _linear32
+    n = int(num_clips)
+    ve, vf = encode_gallery(model, videos, 8, n)                                    # (V*n, 1+N, D), (V*n, 256)
+    te, tf = encode_captions(model, text_input_ids, text_input_mask, text_bsz)      # (C, Lt, D), (C, 256)
+    V, C = ve.shape[0] // n, te.shape[0]
+    sim = _pool_clips(vf @ tf.t() / model.temp, n, score_agg_func)                  # (V*n, C) is clip_pool's layout with A = C
     score = torch.empty(V * C, dtype=torch.float32, device=ve.device)
     ones = torch.ones(ve.shape[:2], dtype=text_input_mask.dtype, device=ve.device)
-    for s in range(0, V * C, pair_bsz):
-        idx = torch.arange(s, min(V * C, s + pair_bsz), device=ve.device)
+    step = max(1, pair_bsz // n)
+    clip = torch.arange(n, device=ve.device)
+    for s in range(0, V * C, step):
+        idx = torch.arange(s, min(V * C, s + step), device=ve.device)
         vi, ci = idx // C, idx % C
+        if n > 1:                                                                   # sequence p * n + j: caption ci[p] with clip j of video vi[p]
+            vi, ci = (vi[:, None] * n + clip).reshape(-1), ci.repeat_interleave(n)
         out = model._fusion(torch.cat([te[ci], ve[vi]], dim=1), torch.cat([text_input_mask[ci], ones[vi]], dim=1))
-        from alpro_amd.modeling.alpro_models import _linear32
-        score[s:s + idx.numel()] = torch.softmax(_linear32(out[:, 0, :], model.itm_head).float(), dim=1)[:, 1]
+        logits = _pool_clips(_linear32(out[:, 0, :], model.itm_head), n, score_agg_func)
+        score[s:s + idx.numel()] = torch.softmax(logits, dim=1)[:, 1]
     return score.view(V, C), sim
 
 
 @torch.no_grad()
-def encode_gallery(model, videos, bsz=8):
-    """Every video through the visual encoder once, `bsz` at a time: videos (V, T, C, H, W) or an iterable of (1, T, C, H, W) clips ->
-    (video_embeds (V, 1+N, D), video_feat (V, 256)), device tensors."""
+def encode_gallery(model, videos, bsz=8, num_clips=1):
+    """Every clip through the visual encoder once, `bsz` at a time: videos (V, n*T, C, H, W) or an iterable of (1, n*T, C, H, W), n = num_clips
+    clips of T frames each -> (video_embeds (V*n, 1+N, D), video_feat (V*n, 256)), row v * n + j, device tensors."""
     model.eval()
-    clips = videos if torch.is_tensor(videos) else torch.cat(list(videos), 0)
+    clips = _split_clips(videos, int(num_clips))
     ve, vf = [], []
     for i in range(0, clips.shape[0], bsz):
         e, f = model.encode_video(clips[i:i + bsz])
@@ -105,31 +135,47 @@ def encode_captions(model, ids, mask, bsz=1024):
 
 
 @torch.no_grad()
-def rerank_retrieval(model, video_embeds, video_feat, text_embeds, text_feat, text_input_mask, k, pair_bsz=512):
+def rerank_retrieval(model, video_embeds, video_feat, text_embeds, text_feat, text_input_mask, k, pair_bsz=512, num_clips=1, score_agg_func="mean"):
     """Two-stage search over cached features (the k_test evaluation of ALBEF / BLIP; the reference itself scores every pair, which
     score_all_pairs reproduces).  Stage 1: the k best videos per caption and the k best captions per video by the 256-d contrastive
     features (hip.sim_topk, scale = 1 / temp: no (V, C) matrix).  Stage 2: only the union of the two candidate sets goes through the
     fusion encoder and the ITM head (model.score_pair_list), every pair once, in the order of vi * C + ci, `pair_bsz` pairs at a time --
     at most 2 k max(V, C) fusion passes instead of V * C.  One host read (the pair count) and the read of `temp`.
+    num_clips = n > 1: video_embeds / video_feat are encode_gallery(..., num_clips=n)'s, (V*n, ...) with row v * n + j.  Stage 1 orders by
+    the POOLED similarity (hip.sim_topk_clips in both directions, still no matrix); stage 2 scores each candidate pair over its n clips
+    (sequences pair-major, max(1, pair_bsz // n) pairs at a time) and pools the logits with hip.clip_pool before the softmax.
     Returns a dict of device tensors: t2v_idx (C, k) int32 video indices, t2v_sim (C, k) similarity / temp, t2v_score (C, k)
     softmax(itm logits)[:, 1]; v2t_idx / v2t_sim / v2t_score (V, k) likewise with caption indices.  Where k exceeds the gallery the tail
     of a row is idx -1, sim -inf, score -inf."""
+    _check_clips(num_clips, score_agg_func)
     from alpro_amd import hip
     model.eval()
-    V, C = video_feat.shape[0], text_feat.shape[0]
+    n = int(num_clips)
+    if video_feat.shape[0] % n:
+        raise ValueError("video_feat has %d rows: not a whole number of videos of num_clips=%d clips" % (video_feat.shape[0], n))
+    V, C = video_feat.shape[0] // n, text_feat.shape[0]
     vf, tf = video_feat.float().contiguous(), text_feat.float().contiguous()
     scale = 1.0 / float(model.temp)
-    t2v_sim, t2v_idx = hip.sim_topk(tf, vf, k, scale=scale)
-    v2t_sim, v2t_idx = hip.sim_topk(vf, tf, k, scale=scale)
+    if n == 1:
+        t2v_sim, t2v_idx = hip.sim_topk(tf, vf, k, scale=scale)
+        v2t_sim, v2t_idx = hip.sim_topk(vf, tf, k, scale=scale)
+    else:
+        t2v_sim, t2v_idx = hip.sim_topk_clips(tf, vf, k, n, side="gallery", mode=score_agg_func, scale=scale)
+        v2t_sim, v2t_idx = hip.sim_topk_clips(vf, tf, k, n, side="query", mode=score_agg_func, scale=scale)
     dev = vf.device
     t2v_pair = t2v_idx.long() * C + torch.arange(C, device=dev)[:, None]          # pair id = vi * C + ci
     v2t_pair = torch.arange(V, device=dev)[:, None] * C + v2t_idx.long()
     t2v_ok, v2t_ok = t2v_idx >= 0, v2t_idx >= 0
     pairs = torch.unique(torch.cat([t2v_pair[t2v_ok], v2t_pair[v2t_ok]]))        # sorted; its length is the one host read
     score = torch.empty(pairs.numel(), dtype=torch.float32, device=dev)
-    for s in range(0, pairs.numel(), pair_bsz):
-        p = pairs[s:s + pair_bsz]
-        logits = model.score_pair_list(video_embeds, text_embeds, text_input_mask, torch.div(p, C, rounding_mode="floor"), p % C)
+    step = max(1, pair_bsz // n)
+    clip = torch.arange(n, device=dev)
+    for s in range(0, pairs.numel(), step):
+        p = pairs[s:s + step]
+        vi, ci = torch.div(p, C, rounding_mode="floor"), p % C
+        if n > 1:                                                                 # sequence i * n + j: clip j of pair p[i]
+            vi, ci = (vi[:, None] * n + clip).reshape(-1), ci.repeat_interleave(n)
+        logits = _pool_clips(model.score_pair_list(video_embeds, text_embeds, text_input_mask, vi, ci), n, score_agg_func)
         score[s:s + p.numel()] = torch.softmax(logits, dim=1)[:, 1]
     ninf = torch.full((), float("-inf"), dtype=torch.float32, device=dev)
 

@@ -636,6 +636,27 @@ size_t alpro_sim_topk_workspace_bytes(int nq, int ng, int k, int chunk);
 int alpro_sim_topk(const float* q, int nq, const float* g, int ng, int d, int k, float scale, int chunk, float* out_val, int32_t* out_idx,
                    void* workspace, size_t workspace_bytes, void* stream);
 
+/* ABI 22: the same search with several clips per video (inference_n_clips > 1, score_agg_func): top-k by POOLED similarity, still without a
+ * matrix.  A video is `clips` (1..ALPRO_TOPK_MAX_CLIPS) consecutive feature rows, row v * clips + j = clip j of video v, on ONE side:
+ *   side ALPRO_TOPK_CLIPS_GALLERY (text -> video): g is (nvid * clips, d), ng % clips == 0; outputs (nq, k), out_idx = the VIDEO index in
+ *     [0, ng / clips).
+ *   side ALPRO_TOPK_CLIPS_QUERY (video -> text): q is (nvid * clips, d), nq % clips == 0; outputs (nq / clips, k), out_idx = the row of g.
+ * Value of a (video, other row) pair: s_j = alpro_sim_topk's fp32 fmaf chain for clip j, x_j = s_j * scale (one fp32 multiply), P = the pool
+ * of x_0 .. x_{clips-1} by `mode` (ALPRO_POOL_MEAN / _MAX / _LSE) with alpro_clip_pool's arithmetic -- one shared device function: mean =
+ * sequential fp32 sum from 0 in ascending j, / (float)clips; max = fmaxf; lse = m + logf(sum_j expf(x_j - m)), m the maximum (no - log clips).
+ * With clips == 1 all three are x_0.  Each output row: the k largest P by (value descending with -0.0 read as +0.0, index ascending), a total
+ * order, so the result does not depend on `chunk`, the grid or the merge order; out_val = P (+0.0 for -0.0); the tail behind the gallery is
+ * idx -1 / val -inf.  NOTE the order is that of P, i.e. after the multiply by scale (alpro_sim_topk orders s and multiplies afterwards).
+ * chunk counts gallery ENTRIES (videos for GALLERY, rows for QUERY): 0 = the library's choice (a function of the shape alone), else a positive
+ * multiple of 32.  d must be 256, 1 <= k <= ALPRO_TOPK_MAX_K.  workspace: 256-byte aligned, at least
+ * alpro_sim_topk_clips_workspace_bytes(...) bytes (0 = the arguments are refused, text in alpro_hip_last_error).  Every argument is checked
+ * before the first HIP call.  No atomics, one writer per output element: bitwise reproducible. */
+#define ALPRO_TOPK_MAX_CLIPS 32
+enum { ALPRO_TOPK_CLIPS_GALLERY = 0, ALPRO_TOPK_CLIPS_QUERY = 1 };
+size_t alpro_sim_topk_clips_workspace_bytes(int nq, int ng, int k, int clips, int side, int chunk);
+int alpro_sim_topk_clips(const float* q, int nq, const float* g, int ng, int d, int k, float scale, int clips, int side, int mode, int chunk,
+                         float* out_val, int32_t* out_idx, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- attention probabilities on request (BertModel.forward output_attentions; xbert.py:323,343) ----
  * out[b][h][q - q0][k - k0] = exp(scale * <q_bhq, k_bhk> + key_bias[b][k] - lse[b][h][q]) for q0 <= q < q0 + nq, k0 <= k < k0 + nk: a window
  * of the (L, L) softmax of every (sequence, head), fp32, (batch, H, nq, nk) contiguous.  qkv (batch*L, 3*H*64) as alpro_gemm wrote it
